@@ -9,7 +9,9 @@ order, first-k-rows rule).  Inputs are resident in HBM before
 the timed region.  value = source payload bytes of all ranks / max-over-
 ranks step time, in GiB/s.
 
-  python bench.py                          # N=1
+  python bench.py                          # N=1: set up, warm up, time the steps, print the line
+  python bench.py --full                   # ... then verification, rooflines and every side leg
+  python bench.py --dump-outputs DIR       # ... and the last step's outputs as DIR/*.npy
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 Multi-GPU: independent generations, each rank encodes/decodes its own G
@@ -113,11 +115,62 @@ def gather_folds(torch, dist, fold: int, world: int, device) -> list:
     return [int(x.item()) & ((1 << 64) - 1) for x in out]
 
 
+DUMP_MAX = 64 * 10**6    # bytes of --dump-outputs, all files together
+DUMP_SAMPLE = 256        # generations whose rows are written
+
+
+def dump_plan(G, r, Lr, emax, Lb) -> tuple[bool, int, int]:
+    """(n_rec and status of every generation?, sampled generations, bytes written) of --dump-outputs."""
+    small = 8 * G <= DUMP_MAX // 4
+    per_gen = 4 * (r * Lr + emax * Lb + emax + 1) + (0 if small else 8)
+    S = max(1, min(G, DUMP_SAMPLE, (DUMP_MAX - (8 * G if small else 0)) // per_gen))
+    return small, S, S * per_gen + (8 * G if small else 0)
+
+
+def dump_outputs(torch, path, rank, rep, rec, rec_index, n_rec, status, G, r, Lr, emax, Lb) -> dict:
+    """--dump-outputs: what a caller of the timed step receives, as float32
+    .npy files.  The row buffers of the headline are 2.6 GB, so the repair
+    rows (r x Lr bytes per generation, zero tail included), the recovered
+    rows and their source indices are written for a seeded sample of
+    generations (`generations.npy`, ascending); n_rec and status for every
+    generation.  The decode defines only the first n_rec recovered rows of a
+    generation: the rows beyond are written as 0 and their indices as -1.
+    Returns {file name: shape}."""
+    small, S, _ = dump_plan(G, r, Lr, emax, Lb)
+    gens = np.sort(np.random.default_rng(SEED ^ 0xD0).choice(G, size=S, replace=False))
+    gsel = torch.from_numpy(gens).to(rep.device)
+    nr = torch.where(status == 0, n_rec, torch.zeros_like(n_rec))
+    valid = torch.arange(emax, device=rep.device)[None, :] < nr[gsel][:, None]          # (S, emax)
+    rec_s = rec.view(G, emax, Lb)[gsel] * valid[..., None]
+    idx_s = torch.where(valid, rec_index.view(G, emax)[gsel].int() & 0xFFFF,
+                        torch.full_like(valid, -1, dtype=torch.int32))
+    arrays = {"generations": gsel, "repairs": rep.view(G, r, Lr)[gsel], "recovered": rec_s, "recovered_index": idx_s,
+              "n_rec": n_rec if small else n_rec[gsel], "status": status if small else status[gsel]}
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(d / f"{name}{sfx}.npy", a)
+        shapes[f"{name}{sfx}.npy"] = list(a.shape)
+    return shapes
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the device round-trip "
+                         "verification, rooflines, the C3 Bernoulli, host-path, CPU, C4, C5 and sliding-halo legs, "
+                         "the run-descriptor broadcast, and the --detail record (the options below that size or "
+                         "skip a leg apply under --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (repair rows, recovered rows and "
+                         "their indices of a seeded sample of generations; n_rec and status of every generation) "
+                         "as DIR/<name>.npy, float32")
     ap.add_argument("--G", type=int, default=None,
                     help="generations per GPU of the headline workload (default 65,536 = C2/C3 at every N; "
                          "156,250 = C4's 10 M packets/GPU with --config c4)")
@@ -253,7 +306,12 @@ def main(argv=None):
         args.G = 156250 if c4 else 65536   # C4: 10,000,000 packets / 64 per generation
     k, r, Lb, G, e = args.k, args.r, args.L, args.G, args.erase
     dev = torch.device("cuda", local)
-    desc_ok = broadcast_descriptor(torch, dist, lib, k, r, Lb, G, e, world, dev if backend == "nccl" else "cpu")
+    # a plain run sets up, warms up, times the steps and prints the line;
+    # every other measurement and check runs under --full
+    full = args.full
+    desc_ok = True
+    if full:
+        desc_ok = broadcast_descriptor(torch, dist, lib, k, r, Lb, G, e, world, dev if backend == "nccl" else "cpu")
     # A dedicated stream for the library AND torch: torch's default stream is
     # handle 0, which the C ABI would replace by a private stream, and the
     # timing events must be recorded on the stream the kernels run on.
@@ -380,12 +438,15 @@ def main(argv=None):
     enc_ms = float(np.mean([a.elapsed_time(b) for a, b, _, _ in ev]))
     dec_ms = float(np.mean([(a if args.overlap else b).elapsed_time(c) for a, b, c, _ in ev]))
     step_ms = wall * 1e3 / args.steps
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(torch, args.dump_outputs, rank, rep, rec, rec_index, n_rec, status, G, r, Lr, emax, Lb)
     # with a second stream the encode shares the GPU with the decode's
     # acceptance pass (split) or the whole decode (overlap): its own roofline
     # comes from a few launches alone, after the timed steps (same buffers and
     # bytes; the repairs are rewritten with the same values)
     enc_alone_ms = None
-    if ctx_enc is not ctx_dec:
+    if full and ctx_enc is not ctx_dec:
         ctx_enc.profile(True)
         for _ in range(5):
             encode()
@@ -396,26 +457,27 @@ def main(argv=None):
         enc_alone_ms = next(iter(ka.values()), None)
 
     # --- verification (size-independent round trip on the device) ---------
-    st_ok = bool((status == 0).all().item())
-    n_ok = bool((n_rec == e).all().item())
-    er_t = torch.from_numpy(erased).to(dev)
-    idx_ok = bool((rec_index.view(G, emax)[:, :e].long() == er_t).all().item())
-    recv = rec.view(G, emax, Lb)[:, :e]
-    gi = torch.arange(G, device=dev)[:, None].expand(-1, e)
-    bytes_ok = bool((recv == srcv[gi, er_t]).all().item())
-    tails_zero = bool((rep.view(G, r, Lr)[:, :, Lb:] == 0).all().item())
-    checksum = int(rep.view(torch.int64).sum().item()) & ((1 << 64) - 1)
-    folds = gather_folds(torch, dist, xor_fold(torch, rep), world, dev if backend == "nccl" else "cpu")
-    verified = st_ok and n_ok and idx_ok and bytes_ok and tails_zero
-
     coll_dev = dev if backend == "nccl" else "cpu"
-    # C4: >= 64 seeded generations per rank against the CPU oracle
-    sample_ok = None
-    if c4 and args.rank_sample > 0:
-        sample_ok = rank_oracle_sample(torch, src, rep, rows, aidx, rec, k, r, Lb, Lr, e, G, args.rank_sample,
-                                       SEED + rank)
-    sample_flags = gather_flags(torch, dist, -1 if sample_ok is None else int(sample_ok), world, coll_dev)
-    desc_flags = gather_flags(torch, dist, int(desc_ok), world, coll_dev)
+    verified, sample_ok = True, None
+    if full:
+        st_ok = bool((status == 0).all().item())
+        n_ok = bool((n_rec == e).all().item())
+        er_t = torch.from_numpy(erased).to(dev)
+        idx_ok = bool((rec_index.view(G, emax)[:, :e].long() == er_t).all().item())
+        recv = rec.view(G, emax, Lb)[:, :e]
+        gi = torch.arange(G, device=dev)[:, None].expand(-1, e)
+        bytes_ok = bool((recv == srcv[gi, er_t]).all().item())
+        tails_zero = bool((rep.view(G, r, Lr)[:, :, Lb:] == 0).all().item())
+        checksum = int(rep.view(torch.int64).sum().item()) & ((1 << 64) - 1)
+        folds = gather_folds(torch, dist, xor_fold(torch, rep), world, coll_dev)
+        verified = st_ok and n_ok and idx_ok and bytes_ok and tails_zero
+
+        # C4: >= 64 seeded generations per rank against the CPU oracle
+        if c4 and args.rank_sample > 0:
+            sample_ok = rank_oracle_sample(torch, src, rep, rows, aidx, rec, k, r, Lb, Lr, e, G, args.rank_sample,
+                                           SEED + rank)
+        sample_flags = gather_flags(torch, dist, -1 if sample_ok is None else int(sample_ok), world, coll_dev)
+        desc_flags = gather_flags(torch, dist, int(desc_ok), world, coll_dev)
     step_ms_max, enc_ms_max, dec_ms_max, fails = reduce_max(
         torch, dist, [step_ms, enc_ms, dec_ms, 0.0 if (verified and sample_ok is not False and desc_ok) else 1.0], world,
         coll_dev)
@@ -567,6 +629,16 @@ def main(argv=None):
         rl["in_step"] = dict(in_step, note="its launches inside the timed steps, beside the decode's acceptance pass")
         return rl
 
+    def finish():
+        if pg:
+            dist.destroy_process_group()
+        if args.split:
+            ctx_dec.close()
+        if args.overlap:
+            ctx_enc.close()
+            ctx_dec.close()
+        ctx.close()
+
     out = {
         "metric": "GF(256) RLNC encode+decode GiB/s device-resident, 1200B pkts gen=64, 1/2/4/8 GPU",
         "value": round(value, 3),
@@ -599,23 +671,32 @@ def main(argv=None):
         # dominant kernel (largest time per step); the fused decode is
         # VALU-issue-bound, its HBM fraction is reported as measured
         # (profiles/ SQ counters)
-        "roofline": roofline(dom),
+        "roofline": roofline(dom) if full else None,
         # the encode kernel BASELINE.json's north star targets (>= 70 % HBM)
-        "roofline_encode": roofline_encode() if enc_kernel else None,
+        "roofline_encode": roofline_encode() if full and enc_kernel else None,
         "streams": ("encode || decode (2 HIP streams)" if args.overlap else
                     ("encode, then decode payload pass on the same stream (qf_ctx_set_payload_stream); decode "
                      "acceptance pass on a 2nd stream beside the encode" if args.payload_stream else
                      "encode, then decode payload pass; decode acceptance pass on a 2nd stream beside the encode")
                     if args.split else "encode then decode (1 stream)"),
-        "verified": bool(fails == 0),
-        "repair_checksum_rank0": checksum,
-        "repair_xor_fold_by_rank": [f"{f:016x}" for f in folds],
         "process_group": {"backend": dist.get_backend() if pg else None,
                           "world_size": dist.get_world_size() if pg else 1,
                           "env_world_size": world},
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if not full:
+        if rank == 0:
+            line = compact_line(out)   # the legs that did not run leave no null entries
+            print(json.dumps({k_: v for k_, v in line.items() if v is not None or k_ == "vs_baseline"}), flush=True)
+        return finish()
+    out.update({
+        "verified": bool(fails == 0),
+        "repair_checksum_rank0": checksum,
+        "repair_xor_fold_by_rank": [f"{f:016x}" for f in folds],
         "run_descriptor": {"broadcast_from_rank0": pg, "fields": ["k", "r", "L", "G", "erased", "seed"],
                            "cauchy_matrix_bytes": r * k, "matches_by_rank": [bool(f == 1) for f in desc_flags]},
-    }
+    })
     if c4:
         out["config"]["workload"] = (f"C4 independent-generation encode + C3-shape decode sharded over {world} rank(s): "
                                      f"k={k}, r={r}, L={Lb}, G={G} generations/rank ({G * k:,} packets/rank), "
@@ -658,14 +739,7 @@ def main(argv=None):
     if rank == 0:
         detail = emit_detail(out, args.detail)
         print(json.dumps(compact_line(out, detail)), flush=True)
-    if pg:
-        dist.destroy_process_group()
-    if args.split:
-        ctx_dec.close()
-    if args.overlap:
-        ctx_enc.close()
-        ctx_dec.close()
-    ctx.close()
+    finish()
 
 
 def c4_leg(torch, dist, fec, L, lib, ctx, stream, dev, rank, world, backend, k, r, Lb, e, G, steps, warmup,
@@ -1443,7 +1517,7 @@ def compact_line(full: dict, detail: str | None = None) -> dict:
                                                                          "decode_gibps")}
     line["roofline_encode"] = _roof_compact(full.get("roofline_encode"))
     for k in ("encode_gibps", "decode_gibps", "encode_ms", "decode_ms", "ms_per_step_median_rank0",
-              "kernel_ms_per_launch", "verified", "process_group"):
+              "kernel_ms_per_launch", "verified", "process_group", "dumped_outputs"):
         if k in full:
             line[k] = full[k]
     line["streams"] = "split" if "2nd stream" in (full.get("streams") or "") else full.get("streams")

@@ -42,6 +42,61 @@ def test_headline_workload_is_per_gpu_constant():
     assert a.G is None and a.config == "auto" and a.c4_G == 156250
 
 
+def test_full_and_dump_outputs_are_off_by_default():
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_sample_mask_and_budget(tmp_path):
+    """--dump-outputs on host tensors: float32 files within DUMP_MAX, the same
+    seeded generations on every call, recovered rows beyond n_rec (and of a
+    failed generation) written as 0 / index -1 whatever the buffer held."""
+    import numpy as np
+    import torch
+    G, r, Lr, emax, Lb = 300, 4, 128, 4, 100
+    rng = np.random.default_rng(1)
+    rep = torch.from_numpy(rng.integers(0, 256, G * r * Lr, dtype=np.uint8))
+    rec = torch.from_numpy(rng.integers(0, 256, G * emax * Lb, dtype=np.uint8))
+    rec_index = torch.from_numpy(rng.integers(0, 64, G * emax).astype(np.int16))
+    n_rec = torch.from_numpy(rng.integers(0, emax + 1, G).astype(np.int32))
+    status = torch.zeros(G, dtype=torch.int32)
+    status[::7] = -3
+    shapes = bench.dump_outputs(torch, str(tmp_path / "a"), 0, rep, rec, rec_index, n_rec, status, G, r, Lr, emax, Lb)
+    S = bench.DUMP_SAMPLE
+    assert shapes == {"generations.npy": [S], "repairs.npy": [S, r, Lr], "recovered.npy": [S, emax, Lb],
+                      "recovered_index.npy": [S, emax], "n_rec.npy": [G], "status.npy": [G]}
+    got = {n: np.load(tmp_path / "a" / n) for n in shapes}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX
+    gens = got["generations.npy"].astype(np.int64)
+    assert (np.diff(gens) > 0).all() and gens.min() >= 0 and gens.max() < G
+    assert (got["repairs.npy"] == rep.numpy().reshape(G, r, Lr)[gens]).all()
+    assert (got["n_rec.npy"] == n_rec.numpy()).all() and (got["status.npy"] == status.numpy()).all()
+    n = np.where(status.numpy() == 0, n_rec.numpy(), 0)[gens]
+    valid = np.arange(emax)[None, :] < n[:, None]
+    assert (got["recovered.npy"] == rec.numpy().reshape(G, emax, Lb)[gens] * valid[..., None]).all()
+    assert (got["recovered_index.npy"] == np.where(valid, rec_index.numpy().reshape(G, emax)[gens], -1)).all()
+    # other bytes in the undefined rows, same files
+    rec2 = rec.clone().view(G, emax, Lb)
+    rec2[torch.from_numpy(np.arange(emax)[None, :] >= np.where(status.numpy() == 0, n_rec.numpy(), 0)[:, None])] = 0xEE
+    bench.dump_outputs(torch, str(tmp_path / "b"), 0, rep, rec2.view(-1), rec_index, n_rec, status, G, r, Lr, emax, Lb)
+    for name in shapes:
+        assert (np.load(tmp_path / "b" / name) == got[name]).all(), name
+
+
+def test_dump_outputs_headline_and_c4_sizes_fit():
+    """The byte budget at the headline's and C4's generation counts."""
+    assert bench.DUMP_MAX <= 64 * 10**6
+    for G, want_small in ((65536, True), (156250, True), (10_000_000, False)):
+        small, S, nbytes = bench.dump_plan(G, 16, 1280, 16, 1200)
+        assert small is want_small and S == bench.DUMP_SAMPLE and nbytes <= bench.DUMP_MAX
+    # jumbo rows: fewer generations, still within the budget
+    small, S, nbytes = bench.dump_plan(4096, 59, 9088, 59, 9000)
+    assert 1 <= S < bench.DUMP_SAMPLE and nbytes <= bench.DUMP_MAX
+
+
 def _recorded_full(name="r04am_bench_full.json"):
     import json
     lines = [l for l in (REPO / "profiles" / name).read_text().splitlines() if l.startswith("{")]

@@ -15,9 +15,10 @@ REPO = Path(__file__).resolve().parent.parent
 
 
 def _run(cmd, env, tmp_path, timeout=170):
-    """Run bench.py; returns (compact stdout line, full detail record)."""
+    """Run bench.py --full (the legs, the verification and the detail record
+    run under it); returns (compact stdout line, full detail record)."""
     detail = tmp_path / "detail.json"
-    p = subprocess.run(cmd + ["--detail", str(detail)], cwd=REPO, env=env, capture_output=True, text=True,
+    p = subprocess.run(cmd + ["--full", "--detail", str(detail)], cwd=REPO, env=env, capture_output=True, text=True,
                        timeout=timeout)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
@@ -25,6 +26,40 @@ def _run(cmd, env, tmp_path, timeout=170):
     import bench  # noqa: F401  (LINE_MAX)
     assert len(lines[0]) <= bench.LINE_MAX, len(lines[0])
     return json.loads(lines[0]), json.loads(detail.read_text())
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the steps and prints the contract keys
+    with no side leg, check or detail record; --dump-outputs writes the last
+    step's outputs: every generation decoded its 13 erased sources, in
+    ascending source order, and the repairs' zero tails are zero."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--G", "1024", "--dump-outputs", str(out)], cwd=tmp_path, env=env, capture_output=True,
+                       text=True, timeout=170)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    # value = source bytes / step time; ms_per_step is rounded to 1e-4 ms (below 1 % of any step of this size)
+    assert abs(line["value"] - 1024 * 64 * 1200 / (line["ms_per_step"] / 1e3) / 2**30) <= 1e-2 * line["value"]
+    for leg in ("roofline", "roofline_encode", "cpu_baseline", "c4", "c5", "c3_bernoulli", "host_path_gibps_incl_pcie",
+                "hbm_copy_gbps", "cpu_variants_gibps", "verified", "detail"):
+        assert leg not in line, leg
+    assert sorted(f.name for f in out.iterdir()) == sorted(line["dumped_outputs"])
+    got = {f.name: np.load(f) for f in out.iterdir()}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert (got["status.npy"] == 0).all() and (got["n_rec.npy"] == 13).all() and got["n_rec.npy"].shape == (1024,)
+    S = len(got["generations.npy"])
+    assert got["repairs.npy"].shape == (S, 16, 1280) and got["recovered.npy"].shape == (S, 16, 1200)
+    assert (got["repairs.npy"][:, :, 1200:] == 0).all() and got["repairs.npy"][:, :, :1200].any()
+    idx = got["recovered_index.npy"]
+    assert (np.diff(idx[:, :13], axis=1) > 0).all() and (idx[:, 13:] == -1).all() and (got["recovered.npy"][:, 13:] == 0).all()
+    assert idx[:, :13].min() >= 0 and idx[:, :13].max() < 64
 
 
 def test_bench_two_ranks_gloo_rehearsal(tmp_path):

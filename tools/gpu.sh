@@ -24,12 +24,12 @@ mkdir -p "$OUT"
 what=${1:-full}
 shift || true
 PYT="python -u -m pytest -x -q --timeout 170 --timeout-method thread"
-ARGS="--steps 20 --warmup 5 --no-cpu --host-path-G 0 --c3b-G 0 --c4-G 0 --c5-mixed-bytes 0"
+ARGS="--full --steps 20 --warmup 5 --no-cpu --host-path-G 0 --c3b-G 0 --c4-G 0 --c5-mixed-bytes 0"
 
 bench_line() {   # $1 log name, rest: bench args
   local name=$1
   shift
-  timeout -k 10 400 python3 bench.py --detail "$OUT/${name}_detail.json" "$@" > "$OUT/$name.log" 2>&1
+  timeout -k 10 400 python3 bench.py --full --detail "$OUT/${name}_detail.json" "$@" > "$OUT/$name.log" 2>&1
   grep '^{"metric"' "$OUT/$name.log" > "$OUT/$name.json"
   echo "$name: $(wc -c < "$OUT/$name.json") bytes"
   cut -c1-300 "$OUT/$name.json"
@@ -76,7 +76,7 @@ case "$what" in
     for i in 1 2; do
       for m in split overlap; do
         X=""; [ "$m" = overlap ] && X="--overlap"
-        timeout -k 10 200 python3 bench.py --no-cpu --c3b-G 0 --host-path-G 0 --c5-mixed-bytes 0 --steps 20 \
+        timeout -k 10 200 python3 bench.py --full --no-cpu --c3b-G 0 --host-path-G 0 --c5-mixed-bytes 0 --steps 20 \
           --warmup 5 --detail "" $X > "$OUT/$m$i.log" 2>&1
       done
     done

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 TAG=${TAG:-r05}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
-BASE="--steps 20 --warmup 5 --no-cpu --host-path-G 0 --c3b-G 0 --c4-G 0 --c5-mixed-bytes 0 --detail /tmp/sweep_detail.json"
+BASE="--full --steps 20 --warmup 5 --no-cpu --host-path-G 0 --c3b-G 0 --c4-G 0 --c5-mixed-bytes 0 --detail /tmp/sweep_detail.json"
 SWEEP=${SWEEP:-"cap256:QF_PREPARE_GRID=0:;cap64:QF_PREPARE_GRID=64:;cap128:QF_PREPARE_GRID=128:;cap512:QF_PREPARE_GRID=512:;serial:QF_PREPARE_GRID=0:--serial"}
 ROUNDS=${ROUNDS:-2}
 : > "$OUT/sweep.jsonl"
