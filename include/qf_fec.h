@@ -322,6 +322,64 @@ int qf_decode_batch_host(qf_ctx *ctx, const qf_decode_shape *shape, uint32_t G,
                          int32_t *status_host);
 
 /* ---------------------------------------------------------------------------
+ * Batched recoding (relay).
+ * No reference counterpart: the reference's nodes either hold all k sources
+ * (Encoder) or decode (Decoder); a relay that holds a mix of systematic and
+ * coded rows of a generation can only forward them.  Recoding emits m fresh
+ * linear combinations of the n rows a relay holds, each with its coefficient
+ * vector over the k sources, without decoding.  A receiver needs no change:
+ * a recoded row enters qf_decode_batch as a row with any index >= k plus its
+ * vector in row_coeffs_dev, qf_decoder_add_packet as a repair packet, and
+ * qf_packet_to_raw as a repair frame (the reference's Decoder takes any
+ * coefficient vector, decoder.rs:694-696).
+ *
+ * For generation g, n = n_rows_dev[g] (NULL: max_rows).  rows_dev,
+ * row_index_dev, n_rows_dev and row_coeffs_dev are laid out as for
+ * qf_decode_batch; all n rows are mixed (no acceptance filtering, duplicates
+ * are legal).  The vector v(s) of slot s over the k sources:
+ *   index < k                       unit vector of that index (row_coeffs not read)
+ *   index >= k, row_coeffs_dev      the k bytes at (g*max_rows + s)*k
+ *   index >= k, no row_coeffs_dev   Cauchy row index - k of (k, r); needs index - k < r
+ * Mix matrix M (m x n): M[j][s] = mix_dev[(g*m + j)*max_rows + s], or with
+ * mix_dev == NULL byte t = (g*m + j)*max_rows + s of what
+ * qf_fill_splitmix_dev(dst, G*m*max_rows, seed, 0) writes (zero bytes kept).
+ * Outputs, j < m:
+ *   out[g][j][t]        = XOR_s M[j][s] * rows[g][s][t], t < L, at
+ *                         out_dev + g*out_gen_stride + j*out_row_stride
+ *                         (exactly L bytes per row are written)
+ *   out_coeffs[g][j][i] = XOR_s M[j][s] * v(s)[i], i < k, at
+ *                         out_coeffs_dev + (g*m + j)*k
+ * status_dev[g]: QF_OK; QF_ENOTREADY when n == 0; QF_EINVAL when n > max_rows
+ * or a row with index >= k has no coefficient vector.  In the non-OK cases
+ * the generation's m rows (L bytes each) and m vectors are written as zeros;
+ * other generations are unaffected.
+ * Returns QF_EINVAL for a bad shape (k, m, max_rows or L out of range, flags
+ * != 0, a row stride shorter than L, a NULL required pointer, pointers or
+ * strides not 16-byte aligned) and QF_ERANGE for k + r > 256.
+ * The payload runs ceil(m / 16) passes of the decode's payload kernel; each
+ * pass reads every input row once.
+ * ------------------------------------------------------------------------- */
+typedef struct qf_recode_shape {
+    uint32_t k;              /* generation size, 1..255 */
+    uint32_t r;              /* Cauchy repairs that may appear among the inputs when
+                                row_coeffs_dev is NULL (k + r <= 256); 0 = none */
+    uint32_t L;              /* payload bytes per row, >= 1 */
+    uint32_t max_rows;       /* input slots per generation, 1..255 */
+    uint32_t m;              /* recoded packets per generation, 1..64 */
+    uint32_t flags;          /* 0 */
+    uint64_t row_stride;     /* inputs, as qf_decode_shape */
+    uint64_t rows_gen_stride;
+    uint64_t out_row_stride;
+    uint64_t out_gen_stride;
+} qf_recode_shape;
+
+int qf_recode_batch(qf_ctx *ctx, const qf_recode_shape *shape, uint32_t G,
+                    const uint8_t *rows_dev, const uint16_t *row_index_dev,
+                    const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                    const uint8_t *mix_dev, uint64_t seed,
+                    uint8_t *out_dev, uint8_t *out_coeffs_dev, int32_t *status_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations

@@ -61,6 +61,15 @@ class DecodeShape(ctypes.Structure):
     ]
 
 
+class RecodeShape(ctypes.Structure):
+    """qf_recode_shape (batched recoding)."""
+    _fields_ = [
+        ("k", _U32), ("r", _U32), ("L", _U32), ("max_rows", _U32), ("m", _U32), ("flags", _U32),
+        ("row_stride", _U64), ("rows_gen_stride", _U64),
+        ("out_row_stride", _U64), ("out_gen_stride", _U64),
+    ]
+
+
 class GenDesc(ctypes.Structure):
     """qf_gen_desc (heterogeneous encode batch)."""
     _fields_ = [
@@ -125,6 +134,7 @@ _SIGS = {
     "qf_decode_batch_desc": (_I, [_P, ctypes.POINTER(DecDesc), _U32, _P, _P, _P, _P, _P, _P]),
     "qf_decode_batch": (_I, [_P, ctypes.POINTER(DecodeShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_decode_batch_host": (_I, [_P, ctypes.POINTER(DecodeShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_recode_batch": (_I, [_P, ctypes.POINTER(RecodeShape), _U32, _P, _P, _P, _P, _P, _U64, _P, _P, _P]),
     "qf_encoder_new": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(_P)]),
     "qf_encoder_free": (_I, [_P]),
     "qf_encoder_add_source_packet": (_I, [_P, _U64, _P, _U32]),

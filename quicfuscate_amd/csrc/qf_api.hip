@@ -1080,6 +1080,10 @@ int ctx_gf16_zech(qf_ctx* ctx, const uint16_t** zech) {
     *zech = lg + 65536;
     return QF_OK;
 }
+const uint8_t* ctx_explog(qf_ctx* ctx) { return ctx->d_explog; }
+hipError_t ctx_combine_payload(qf_ctx* ctx, const CombineSlotsArgs& a, hipStream_t st, std::string* name) {
+    return combine_payload(ctx, a, pick_PD(ctx, QF_OPT_DECODE_PD, 1), st, name);
+}
 hipEvent_t ctx_prof_begin(qf_ctx* ctx, hipStream_t st) { return prof_begin(ctx, st); }
 void ctx_prof_end(qf_ctx* ctx, hipStream_t st, hipEvent_t ev, const std::string& name) {
     prof_end(ctx, st, ev, name);

@@ -135,6 +135,38 @@ hipError_t launch_mul_slice(const uint8_t* a, const uint8_t* b, uint8_t* out, ui
                             const uint8_t* explog, int num_cus, hipStream_t st);
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t n, uint64_t seed, uint64_t word_offset,
                                 int num_cus, hipStream_t st);
+// The generator of qf_fill_splitmix_dev: byte t of a region is byte (t & 7),
+// little endian, of splitmix64(seed + word_offset + t / 8).  Shared by
+// k_fill_splitmix and the seeded mix of k_recode_prepare (qf_recode.hip).
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// Recode control (qf_recode_batch, qf_recode.hip): one wave per generation
+// builds the m x n mix matrix (explicit or seeded), the payload pass's
+// coefficient records [pass][G][(max_rows + 1) * 16] (record max_rows all
+// zero), n_out = m, bound = n (0 for a generation whose status is not QF_OK),
+// and the recoded coefficient vectors out_coeffs[g][j][0..k).
+struct RecodePrepareArgs {
+    const uint16_t* row_index;   // [G][max_rows]
+    const uint32_t* n_rows;      // [G] or nullptr (= max_rows)
+    const uint8_t* row_coeffs;   // [G][max_rows][k] or nullptr (Cauchy rows of (k, r))
+    const uint8_t* mix;          // [G][m][max_rows] or nullptr (seeded)
+    const uint8_t* explog;       // exp[512] then log[256]
+    uint64_t seed;
+    uint8_t* coef_out;
+    uint64_t coef_gen_stride;
+    uint32_t* n_out;
+    uint32_t* bound;
+    uint8_t* out_coeffs;         // [G][m][k]
+    int32_t* status;
+    uint32_t k, r, m, max_rows, passes, G;
+};
+size_t recode_prepare_lds_bytes(uint32_t k, uint32_t m, uint32_t max_rows);
+hipError_t launch_recode_prepare(const RecodePrepareArgs& a, hipStream_t st);
 
 // One encoder window of a multi-connection send batch: the window's ring at
 // src + src_off (position i in slot (rot + i) % k), its repairs at

@@ -1439,13 +1439,7 @@ __global__ void __launch_bounds__(1024) k_mul_slice_tab(const uint8_t* __restric
         out[t] = tab[(uint32_t)a[t] << 8 | b[t]];
 }
 
-QF_DEV uint64_t splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
+// (splitmix64: qf_kernels.h, shared with k_recode_prepare)
 __global__ void __launch_bounds__(256) k_fill_splitmix(uint8_t* __restrict__ dst, uint64_t n,
                                                        uint64_t seed, uint64_t word_offset) {
     const uint64_t nw = n / 8;

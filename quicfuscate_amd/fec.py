@@ -35,7 +35,7 @@ _atexit.register(_mark_shutdown)
 __all__ = [
     "QfError", "Context", "default_context", "init_gf_tables", "gf_mul", "gf_mul_table",
     "gf_mul_add", "gf_inv", "gf_mul_slice", "cauchy_coefficients", "MemoryPool", "Packet",
-    "Encoder", "Decoder", "encode_batch", "decode_batch",
+    "Encoder", "Decoder", "encode_batch", "decode_batch", "recode_batch", "Recoder",
     "gf16_mul", "gf16_inv", "cauchy16_coefficients", "encode16_batch", "decode16_batch", "Encoder16", "Decoder16",
 ]
 
@@ -361,6 +361,35 @@ def decode_batch(rows, row_index, rec, rec_index, n_rec, status, k: int, r: int,
         _ptr(n_rec), _ptr(status)), "decode_batch")
 
 
+def recode_batch(rows, row_index, out, out_coeffs, status, k: int, m: int, Lb: int, *, r: int = 0,
+                 max_rows: int, row_stride: int, rows_gen_stride: int, out_row_stride: int,
+                 out_gen_stride: int, G: int, n_rows=None, row_coeffs=None, mix=None, seed: int = 0,
+                 ctx: Optional[Context] = None) -> None:
+    """qf_recode_batch: m fresh linear combinations of the rows a relay holds
+    of each of G generations, with their coefficient vectors over the k
+    sources (out_coeffs: [G, m, k] bytes).  Inputs as decode_batch; mix:
+    optional [G, m, max_rows] bytes, else the splitmix64 stream of `seed`."""
+    _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(out, _span(G, out_gen_stride, m, out_row_stride, Lb), "out")
+    _need(out_coeffs, G * m * k, "out_coeffs (m vectors of k bytes per generation)")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if row_coeffs is not None:
+        _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    if mix is not None:
+        _need(mix, G * m * max_rows, "mix")
+    ctx = ctx or default_context()
+    sh = L.RecodeShape(k, r, Lb, max_rows, m, 0, row_stride, rows_gen_stride, out_row_stride, out_gen_stride)
+    check(L._lib().qf_recode_batch(
+        ctx.handle, ctypes.byref(sh), G, _ptr(rows), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None,
+        _ptr(row_coeffs) if row_coeffs is not None else None,
+        _ptr(mix) if mix is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _ptr(out), _ptr(out_coeffs), _ptr(status)), "recode_batch")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
@@ -581,6 +610,80 @@ class Decoder:
             L._lib().qf_decoder_free(self.handle)
         except Exception:
             pass
+
+
+class Recoder:
+    """A relay's view of one generation (no reference counterpart): it keeps
+    the packets it receives, systematic or coded, in a device buffer and emits
+    fresh linear combinations of them through recode_batch (G = 1).  Every
+    recoded packet carries its coefficient vector over the k sources, so an
+    unmodified Decoder takes it as a repair packet.  No CPU fallback."""
+
+    def __init__(self, k: int, max_len: int, capacity: int, ctx: Optional[Context] = None):
+        import torch
+
+        if not (1 <= k <= 255 and 1 <= capacity <= 255 and max_len >= 1):
+            raise QfError(L.QF_EINVAL, "Recoder: k, capacity in 1..255, max_len >= 1")
+        self.k, self.max_len, self.capacity = k, max_len, capacity
+        self.ctx = ctx or default_context()
+        self.stride = (max_len + 15) // 16 * 16
+        dev = f"cuda:{self.ctx.device}"
+        self._rows = torch.zeros(capacity * self.stride, dtype=torch.uint8, device=dev)
+        self._index = torch.zeros(capacity, dtype=torch.int16, device=dev)
+        self._coeffs = torch.zeros(capacity * k, dtype=torch.uint8, device=dev)
+        self.count = 0
+        self._len = 0   # longest payload held: the length of the recoded packets
+
+    def add_packet(self, packet: Packet) -> None:
+        """Stores a systematic packet (column id % k, decoder.rs:684) or a
+        coded one (its k coefficient bytes); shorter payloads count as zero
+        padded, as in the encoder's window."""
+        import torch
+
+        if self.count >= self.capacity:
+            raise QfError(L.QF_ETOOSMALL, "Recoder: capacity reached")
+        data = packet.payload()
+        if len(data) > self.max_len:
+            raise QfError(L.QF_EINVAL, "Recoder: packet longer than max_len")
+        s = self.count
+        if packet.is_systematic:
+            index = packet.id % self.k
+        else:
+            if packet.coefficients is None or packet.coeff_len != self.k:
+                raise QfError(L.QF_EINVAL, "Repair packet missing coefficients.")
+            index = self.k
+            co = torch.frombuffer(bytearray(packet.coefficients[: self.k]), dtype=torch.uint8)
+            self._coeffs[s * self.k: (s + 1) * self.k].copy_(co)
+        row = torch.frombuffer(bytearray(data.ljust(self.stride, b"\0")), dtype=torch.uint8)
+        self._rows[s * self.stride: (s + 1) * self.stride].copy_(row)
+        self._index[s: s + 1].fill_(index)
+        self.count += 1
+        self._len = max(self._len, len(data))
+
+    def recode(self, count: int, seed: int, first_id: int = 0) -> list:
+        """`count` (1..64) recoded packets of the rows held, ids first_id ..;
+        an empty list while nothing is held.  Non-systematic packets with
+        coefficients (coeff_len = k)."""
+        import torch
+
+        if self.count == 0 or self._len == 0:
+            return []
+        dev = self._rows.device
+        k, stride = self.k, self.stride
+        out = torch.empty(count * stride, dtype=torch.uint8, device=dev)
+        oc = torch.empty(count * k, dtype=torch.uint8, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        n_rows = torch.full((1,), self.count, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(self.ctx.device).synchronize()
+        recode_batch(self._rows, self._index, out, oc, status, k, count, self._len, max_rows=self.capacity,
+                     row_stride=stride, rows_gen_stride=self.capacity * stride, out_row_stride=stride,
+                     out_gen_stride=count * stride, G=1, n_rows=n_rows, row_coeffs=self._coeffs, seed=seed,
+                     ctx=self.ctx)
+        self.ctx.sync()
+        check(int(status.cpu()[0]), "Recoder.recode")
+        raw, cb = out.cpu().numpy().tobytes(), oc.cpu().numpy().tobytes()
+        return [Packet(first_id + j, bytearray(raw[j * stride: j * stride + self._len]), self._len, False,
+                       cb[j * k: (j + 1) * k], k) for j in range(count)]
 
 
 # ---------------------------------------------------------------------------
