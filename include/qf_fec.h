@@ -66,6 +66,14 @@ int qf_gf256_inv(uint8_t a, uint8_t *out);
  * repairs 0..r-1: out[j*k + i] = inv((u8)i ^ (u8)(k + j)).  QF_ERANGE where
  * the reference panics (k + r > 256). */
 int qf_cauchy_coeffs(uint32_t k, uint32_t r, uint8_t *out_rxk);
+/* No reference counterpart (the rule of qf_rank_batch below, on the host, no
+ * device needed): n vectors of k bytes in arrival order, vectors_nxk[s*k + i].
+ * innovative_out[s] (may be NULL) = 1 iff vector s is not in the GF(2^8) span
+ * of vectors 0..s-1, *rank_out = the number of such vectors.  Plain
+ * arrival-order elimination with table arithmetic.  QF_EINVAL for k == 0, a
+ * NULL rank_out, or NULL vectors with n > 0. */
+int qf_gf256_rank(uint32_t k, uint32_t n, const uint8_t *vectors_nxk,
+                  uint8_t *innovative_out, uint32_t *rank_out);
 
 /* ---------------------------------------------------------------------------
  * Context
@@ -279,8 +287,9 @@ int qf_encode_batch_host(qf_ctx *ctx, const qf_encode_shape *shape, uint32_t G,
  *    (the packet's coefficient block, decoder.rs:694-696)
  *  - n_rows_dev: per-generation slot count, or NULL (= max_rows)
  * Acceptance follows decoder.rs:678-701: the first k rows win, duplicate
- * systematic rows are ignored.  For each generation the erased source rows
- * are recovered (ascending source index) into
+ * systematic rows are ignored (rows that may be linearly dependent, as
+ * recoded traffic is: qf_decode_innovative_batch below).  For each generation
+ * the erased source rows are recovered (ascending source index) into
  *   rec_dev + g*rec_gen_stride + m*rec_row_stride,  m < n_rec[g] <= min(k, r)
  * with rec_index_dev[g*min(k,r) + m] = source index of recovered row m and
  * status_dev[g] = QF_OK / QF_ENOTREADY / QF_ERANK / QF_ERANGE / QF_EINVAL.
@@ -380,6 +389,70 @@ int qf_recode_batch(qf_ctx *ctx, const qf_recode_shape *shape, uint32_t G,
                     uint8_t *out_dev, uint8_t *out_coeffs_dev, int32_t *status_dev);
 
 /* ---------------------------------------------------------------------------
+ * Rank-aware receive side for recoded traffic (opt-in extension).
+ * No reference counterpart: the reference's Cauchy code makes any k distinct
+ * rows independent, so its decoder takes the first k rows (decoder.rs:678-701)
+ * and so does qf_decode_batch.  Recoded traffic (qf_recode_batch) carries
+ * dependent rows as a matter of course; these calls apply the RLNC receive
+ * rule instead: a row is accepted iff it is innovative.
+ *
+ * For generation g the slots s = 0 .. n-1 are taken in arrival order, with
+ * n = min(n_rows_dev[g], max_rows) (NULL: max_rows) and the layouts of
+ * qf_decode_batch.  The vector v(s) over the k sources is that of
+ * qf_recode_batch:
+ *   index < k                       unit vector of that index
+ *   index >= k, row_coeffs_dev      the k bytes at (g*max_rows + s)*k; needs index - k < 256
+ *   index >= k, no row_coeffs_dev   Cauchy row index - k of (k, r); needs index - k < r
+ * A slot that breaks its "needs" gives the generation QF_EINVAL.  Slot s is
+ * innovative iff v(s) is not in the GF(2^8) span of v(0) .. v(s-1): a zero
+ * vector, a repeated systematic or Cauchy index, and every row after the rank
+ * has reached k are not.  rank[g] = number of innovative slots.
+ *
+ * qf_rank_batch (control only, no payload):
+ *   innovative_dev[g*max_rows + s] = 1 / 0 (0 for s >= n); may be NULL
+ *   rank_dev[g]                    = rank of generation g
+ *   status_dev[g]                  = QF_OK, or QF_EINVAL (rank and flags 0)
+ * Returns QF_EINVAL for k outside 1..256, max_rows outside 1..4096, flags != 0
+ * or a NULL required pointer, and QF_ERANGE for NULL row_coeffs_dev with r > 0
+ * and k + r > 256.
+ * ------------------------------------------------------------------------- */
+typedef struct qf_rank_shape {
+    uint32_t k;              /* generation size, 1..256 */
+    uint32_t r;              /* Cauchy repairs that may appear when row_coeffs_dev is NULL */
+    uint32_t max_rows;       /* slots per generation, 1..4096 */
+    uint32_t flags;          /* 0 */
+} qf_rank_shape;
+
+int qf_rank_batch(qf_ctx *ctx, const qf_rank_shape *shape, uint32_t G,
+                  const uint16_t *row_index_dev, const uint32_t *n_rows_dev,
+                  const uint8_t *row_coeffs_dev, uint8_t *innovative_dev,
+                  uint32_t *rank_dev, int32_t *status_dev);
+
+/* qf_decode_batch over the innovative slots only: generation g's rec,
+ * rec_index, n_rec and status are exactly what qf_decode_batch writes for the
+ * same generation with the non-innovative slots removed and the order kept.
+ * The accepted rows are independent, so QF_ERANK is never reported; rank < k
+ * gives QF_ENOTREADY with n_rec = 0.  An erased source is one without an
+ * accepted systematic row, which includes a systematic row dropped because
+ * earlier coded rows already span it; more than min(k, r) of them is
+ * QF_EINVAL.  The payload of a non-innovative slot reaches no output.
+ * rank_dev and innovative_dev (both nullable) receive what qf_rank_batch
+ * writes (the rank is reported for QF_ENOTREADY generations as well).
+ * Shape limits, alignment rules and error returns are those of
+ * qf_decode_batch's general path (k <= 256, min(k, r) <= 128, max_rows <=
+ * 4096, 16-byte alignment), plus QF_ERANGE for NULL row_coeffs_dev with r > 0
+ * and k + r > 256.  The call always runs that general path (the acceptance
+ * kernel k_rank_filter, k_decode_prepare and the payload pass), also with
+ * NULL row_coeffs_dev: pure Cauchy traffic keeps using qf_decode_batch and
+ * its fused kernels.  It does not honour qf_ctx_set_payload_stream /
+ * qf_ctx_set_payload_wait; it clears them, as the _host and _desc calls do. */
+int qf_decode_innovative_batch(qf_ctx *ctx, const qf_decode_shape *shape, uint32_t G,
+                               const uint8_t *rows_dev, const uint16_t *row_index_dev,
+                               const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                               uint8_t *rec_dev, uint16_t *rec_index_dev, uint32_t *n_rec_dev,
+                               int32_t *status_dev, uint32_t *rank_dev, uint8_t *innovative_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations
@@ -461,6 +534,20 @@ int qf_decoder_strategy(const qf_decoder *dec);
  * verified and exact elimination decided); 0 before any
  * Wiedemann solve and for k <= 256 decoders. */
 int qf_decoder_solve_attempts(const qf_decoder *dec);
+/* No reference counterpart (opt-in, off by default): with the mode on,
+ * qf_decoder_add_packet takes a packet only if it is innovative (the rule of
+ * qf_rank_batch) and drops any other one, returning 0.  The decision is made
+ * on the host against an incremental basis of at most k * k bytes (the
+ * elimination of qf_gf256_rank), no device call per packet.  The k rows kept
+ * are then independent, so the generation decodes when the rank reaches k.  A
+ * systematic packet dropped because coded packets already span it is
+ * reconstructed like any erased source (out_ids[i] = i).  QF_EINVAL for NULL,
+ * for k > 256 decoders and once a packet has been accepted. */
+int qf_decoder_set_innovative(qf_decoder *dec, int on);
+/* Rank of the packets accepted so far (0..k).  With the mode on it is the
+ * number of accepted packets; with the mode off it is computed on the host
+ * from the stored rows on each call.  QF_EINVAL for NULL and k > 256. */
+int qf_decoder_rank(const qf_decoder *dec);
 int qf_decoder_free(qf_decoder *dec);
 /* replaces decoder.rs:678 Decoder::add_packet.  Returns 1 when the generation
  * is decoded, 0 when more packets are needed, QF_EINVAL for a repair packet

@@ -70,6 +70,11 @@ class RecodeShape(ctypes.Structure):
     ]
 
 
+class RankShape(ctypes.Structure):
+    """qf_rank_shape (innovative-row filter)."""
+    _fields_ = [("k", _U32), ("r", _U32), ("max_rows", _U32), ("flags", _U32)]
+
+
 class GenDesc(ctypes.Structure):
     """qf_gen_desc (heterogeneous encode batch)."""
     _fields_ = [
@@ -135,6 +140,12 @@ _SIGS = {
     "qf_decode_batch": (_I, [_P, ctypes.POINTER(DecodeShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_decode_batch_host": (_I, [_P, ctypes.POINTER(DecodeShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_recode_batch": (_I, [_P, ctypes.POINTER(RecodeShape), _U32, _P, _P, _P, _P, _P, _U64, _P, _P, _P]),
+    "qf_gf256_rank": (_I, [_U32, _U32, _P, _P, _P]),
+    "qf_rank_batch": (_I, [_P, ctypes.POINTER(RankShape), _U32, _P, _P, _P, _P, _P, _P]),
+    "qf_decode_innovative_batch": (_I, [_P, ctypes.POINTER(DecodeShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _P, _P]),
+    "qf_decoder_set_innovative": (_I, [_P, _I]),
+    "qf_decoder_rank": (_I, [_P]),
     "qf_encoder_new": (_I, [_P, _U32, _U32, _U32, ctypes.POINTER(_P)]),
     "qf_encoder_free": (_I, [_P]),
     "qf_encoder_add_source_packet": (_I, [_P, _U64, _P, _U32]),

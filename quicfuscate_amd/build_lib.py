@@ -29,7 +29,7 @@ LIB = OUT_DIR / "libqf_fec.so"
 LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
-           "qf_gf16_fft.hip", "qf_recode.hip"]
+           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -427,7 +427,7 @@ def build(verbose: bool = False) -> Path:
         futs = {
             s: ex.submit(_compile, s, build_dir,
                          ["-Rpass-analysis=kernel-resource-usage"]
-                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip")
+                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip")
                          else [])
             for s in SOURCES
         }
@@ -443,6 +443,15 @@ def build(verbose: bool = False) -> Path:
                 ru = _check_no_scratch(err)
                 if any(u.get("ScratchSize", 0) for u in ru.values()):
                     raise RuntimeError(f"k_recode_prepare uses scratch: {ru}")
+                if verbose:
+                    for n, u in sorted(ru.items()):
+                        print(f"  {n}: {u}")
+            if s == "qf_rank.hip":
+                # k_rank_filter keeps the incoming vector in registers and the
+                # basis in LDS: no scratch
+                ru = _check_no_scratch(err)
+                if any(u.get("ScratchSize", 0) for u in ru.values()):
+                    raise RuntimeError(f"k_rank_filter uses scratch: {ru}")
                 if verbose:
                     for n, u in sorted(ru.items()):
                         print(f"  {n}: {u}")

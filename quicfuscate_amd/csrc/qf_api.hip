@@ -1415,10 +1415,18 @@ int qf_encode_batch_host(qf_ctx* ctx, const qf_encode_shape* sh, uint32_t G, con
     return QF_OK;
 }
 
+// qf_decode_innovative_batch: the general path with k_rank_filter's flags as
+// k_decode_prepare's accept mask; rank / innovative are the caller's optional
+// outputs (the flags live in the workspace when innovative is NULL)
+struct InnovativeOut {
+    uint32_t* rank;
+    uint8_t* innovative;
+};
+
 static int decode_batch_impl(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const uint8_t* rows,
                              const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
                              uint8_t* rec, uint16_t* rec_index, uint32_t* n_rec, int32_t* status,
-                             bool locked = false);
+                             bool locked = false, const InnovativeOut* inv = nullptr);
 
 int qf_decode_batch(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const uint8_t* rows,
                     const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
@@ -1437,6 +1445,23 @@ int qf_decode_batch(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const ui
     ctx->payload_wait = nullptr;  // one decode call only, whatever its outcome
     ctx->has_payload_stream = ctx->payload_on_stream = false;
     return s;
+}
+
+int qf_decode_innovative_batch(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const uint8_t* rows,
+                               const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                               uint8_t* rec, uint16_t* rec_index, uint32_t* n_rec, int32_t* status,
+                               uint32_t* rank, uint8_t* innovative) {
+    if (!ctx || !sh) return QF_EINVAL;
+    {   // qf_ctx_set_payload_stream / _wait apply to qf_decode_batch only
+        std::lock_guard<std::mutex> g(ctx->mu);
+        ctx->has_payload_stream = ctx->payload_on_stream = false;
+        ctx->payload_wait = nullptr;
+    }
+    // (the Cauchy row of index - k is defined for k + r <= 256 only)
+    if (!row_coeffs && sh->r && sh->k >= 1 && sh->k <= 256 && (uint64_t)sh->k + sh->r > 256) return QF_ERANGE;
+    const InnovativeOut inv{rank, innovative};
+    return decode_batch_impl(ctx, sh, G, rows, row_index, n_rows, row_coeffs, rec, rec_index, n_rec, status, false,
+                             &inv);
 }
 
 int qf_ctx_set_payload_stream(qf_ctx* ctx, void* stream) {
@@ -1567,7 +1592,7 @@ int qf_decode_batch_host(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, con
 static int decode_batch_impl(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const uint8_t* rows,
                              const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
                              uint8_t* rec, uint16_t* rec_index, uint32_t* n_rec, int32_t* status,
-                             bool locked) {
+                             bool locked, const InnovativeOut* inv) {
     if (!ctx || !sh) return QF_EINVAL;
     const uint32_t k = sh->k, r = sh->r, L = sh->L, max_rows = sh->max_rows;
     if (k == 0 || k > 256 || max_rows == 0 || max_rows > 4096 || L == 0) return QF_EINVAL;
@@ -1583,7 +1608,7 @@ static int decode_batch_impl(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G,
     if (!locked) g.lock();
     int s = ensure_device(ctx);
     if (s) return s;
-    if (!row_coeffs && ctx->opt[QF_OPT_BITSLICED] && r <= 16 && k + r <= 256 && qf::syn_available(k, r) &&
+    if (!inv && !row_coeffs && ctx->opt[QF_OPT_BITSLICED] && r <= 16 && k + r <= 256 && qf::syn_available(k, r) &&
         max_rows <= 255 && L >= 32 && sh->rows_gen_stride < (1ull << 32) &&
         sh->row_stride < (1ull << 32) && (uint64_t)G * qf::bs_padded_units(L) < (1ull << 31) &&
         (uint64_t)r * 16 * qf::bs_padded_units(L) < (1ull << 32)) {
@@ -1605,19 +1630,40 @@ static int decode_batch_impl(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G,
     }
     // codes without a syndrome kernel but with encode kernels (C5 Medium
     // windows: r up to 64): syndromes through the encode kernels
-    if (!row_coeffs && ctx->opt[QF_OPT_BITSLICED] && !qf::syn_available(k, r) && qf::bs_available(k, r) && r <= 64 &&
-        e_max <= 64 && k + r <= 256 && max_rows <= 255 && L >= 32 && sh->rows_gen_stride < (1ull << 32) &&
+    if (!inv && !row_coeffs && ctx->opt[QF_OPT_BITSLICED] && !qf::syn_available(k, r) && qf::bs_available(k, r) &&
+        r <= 64 && e_max <= 64 && k + r <= 256 && max_rows <= 255 && L >= 32 && sh->rows_gen_stride < (1ull << 32) &&
         sh->row_stride < (1ull << 32) && (uint64_t)G * qf::bs_padded_units(L) < (1ull << 31))
         return decode_cauchy_enc(ctx, sh, G, rows, row_index, n_rows, rec, rec_index, n_rec, status);
     const uint32_t passes = (e_max + 15) / 16;
     const uint64_t coef_gen_stride = ((uint64_t)max_rows + 1) * 16;
     const size_t coef_bytes = (size_t)std::max<uint32_t>(passes, 1) * G * coef_gen_stride;
     const size_t bound_off = round_up(coef_bytes, 256);
-    s = grow_work(ctx, bound_off + (size_t)G * 4);
+    // (innovative decode: the filter's flags after the bounds, unless the caller takes them)
+    const size_t flags_off = round_up(bound_off + (size_t)G * 4, 256);
+    const size_t work_bytes = inv && !inv->innovative ? flags_off + (size_t)G * max_rows : bound_off + (size_t)G * 4;
+    s = grow_work(ctx, work_bytes);
     if (s) return s;
     uint8_t* d_coef = ctx->d_work;
     uint32_t* d_bound = reinterpret_cast<uint32_t*>(ctx->d_work + bound_off);
     qf::PrepareArgs pa{};
+    if (inv) {
+        qf::RankFilterArgs fa{};
+        fa.row_index = row_index;
+        fa.n_rows = n_rows;
+        fa.row_coeffs = row_coeffs;
+        fa.explog = ctx->d_explog;
+        fa.innovative = inv->innovative ? inv->innovative : ctx->d_work + flags_off;
+        fa.rank = inv->rank;
+        fa.status = nullptr;   // k_decode_prepare applies the same index rules and reports
+        fa.k = k;
+        fa.r = r;
+        fa.max_rows = max_rows;
+        fa.G = G;
+        hipEvent_t evf = prof_begin(ctx, ctx->stream);
+        QF_CHECK_HIP(qf::launch_rank_filter(fa, ctx->stream));
+        prof_end(ctx, ctx->stream, evf, "k_rank_filter");
+        pa.accept = fa.innovative;
+    }
     pa.row_index = row_index;
     pa.n_rows = n_rows;
     pa.row_coeffs = row_coeffs;

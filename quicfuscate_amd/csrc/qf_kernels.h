@@ -74,6 +74,9 @@ struct PrepareArgs {
     uint32_t max_rows_pad;
     uint32_t passes;
     uint32_t G;
+    // qf_decode_innovative_batch: [G][max_rows] accept flags of k_rank_filter;
+    // a slot is a candidate only if its byte is set (nullptr: every slot)
+    const uint8_t* accept = nullptr;
 };
 
 // Decode control for the reference's Cauchy code (no row_coeffs): row
@@ -167,6 +170,23 @@ struct RecodePrepareArgs {
 };
 size_t recode_prepare_lds_bytes(uint32_t k, uint32_t m, uint32_t max_rows);
 hipError_t launch_recode_prepare(const RecodePrepareArgs& a, hipStream_t st);
+
+// Innovative-row filter (qf_rank_batch, qf_decode_innovative_batch;
+// qf_rank.hip): one wave per generation walks the slots in arrival order and
+// flags the rows that raise the rank (k <= 256, max_rows <= 4096; without
+// row_coeffs k + r <= 256).  An invalid generation gets rank 0 and no flags.
+struct RankFilterArgs {
+    const uint16_t* row_index;   // [G][max_rows]
+    const uint32_t* n_rows;      // [G] or nullptr (= max_rows)
+    const uint8_t* row_coeffs;   // [G][max_rows][k] or nullptr (Cauchy rows of (k, r))
+    const uint8_t* explog;       // exp[512] then log[256]
+    uint8_t* innovative;         // [G][max_rows] or nullptr
+    uint32_t* rank;              // [G] or nullptr
+    int32_t* status;             // [G] or nullptr
+    uint32_t k, r, max_rows, G;
+};
+size_t rank_filter_lds_bytes(uint32_t k);
+hipError_t launch_rank_filter(const RankFilterArgs& a, hipStream_t st);
 
 // One encoder window of a multi-connection send batch: the window's ring at
 // src + src_off (position i in slot (rot + i) % k), its repairs at

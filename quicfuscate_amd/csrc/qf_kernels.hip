@@ -612,11 +612,15 @@ __global__ void __launch_bounds__(64) k_decode_prepare(PrepareArgs a) {
     __syncthreads();
     const uint32_t n = a.n_rows ? min(a.n_rows[g], a.max_rows) : a.max_rows;
     const uint16_t* ridx = a.row_index + (uint64_t)g * a.max_rows;
+    // accept flags of k_rank_filter (qf_decode_innovative_batch): a slot
+    // without its flag is no candidate; index validity covers every slot
+    const uint8_t* acpt = a.accept ? a.accept + (uint64_t)g * a.max_rows : nullptr;
     bool bad = false;
     for (uint32_t s = lane; s < n; s += 64) {
         const uint32_t idx = ridx[s];
-        if (idx < k) atomicMin(&L.first[idx], s);
-        else if (idx - k >= a.rep_limit) bad = true;
+        if (idx < k) {
+            if (!acpt || acpt[s]) atomicMin(&L.first[idx], s);
+        } else if (idx - k >= a.rep_limit) bad = true;
     }
     for (uint32_t s = lane; s < a.max_rows; s += 64) L.slot_col[s] = 0xFFFF;
     __syncthreads();
@@ -632,6 +636,7 @@ __global__ void __launch_bounds__(64) k_decode_prepare(PrepareArgs a) {
         if (s < n) {
             idx = ridx[s];
             cand = idx >= k ? (idx - k < a.rep_limit) : (L.first[idx] == s);
+            if (acpt && !acpt[s]) cand = false;
         }
         const uint64_t bc = __ballot(cand);
         const uint32_t pos = accepted + __popcll(bc & lt_mask);

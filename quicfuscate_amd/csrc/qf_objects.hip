@@ -101,6 +101,11 @@ struct qf_decoder {
     uint8_t* d_wrec = nullptr;
     uint32_t wrec_rows = 0;
     uint32_t w_tries = 0;           // init vectors the last Wiedemann solve used
+    // qf_decoder_set_innovative: a packet is accepted only if its vector
+    // raises the rank of the accepted ones (host elimination, qf_rank.hip)
+    bool innovative = false;
+    qf::RankBasis basis;
+    std::vector<uint8_t> vec;       // k: the candidate's vector
 };
 
 namespace {
@@ -384,6 +389,28 @@ int qf_decoder_solve_attempts(const qf_decoder* d) {
     return (int)d->w_tries;
 }
 
+int qf_decoder_set_innovative(qf_decoder* d, int on) {
+    if (!d || d->k > 256 || d->accepted > 0) return QF_EINVAL;
+    d->innovative = on != 0;
+    if (d->innovative) d->basis.reset(d->k);
+    return QF_OK;
+}
+
+int qf_decoder_rank(const qf_decoder* d) {
+    if (!d || d->k > 256) return QF_EINVAL;
+    if (d->innovative) return (int)d->basis.rank();
+    // mode off: the rank of the rows held, by the same elimination
+    const uint32_t k = d->k;
+    std::vector<uint8_t> V((size_t)d->accepted * k, 0);
+    for (uint32_t q = 0; q < d->accepted; ++q) {
+        if (d->index[q] < k) V[(size_t)q * k + d->index[q]] = 1;
+        else memcpy(&V[(size_t)q * k], &d->coeffs[(size_t)q * k], k);
+    }
+    uint32_t rank = 0;
+    const int s = qf_gf256_rank(k, d->accepted, V.data(), nullptr, &rank);
+    return s != QF_OK ? s : (int)rank;
+}
+
 // How the k accepted rows decode (decoder.rs:704-783): repair rows that are
 // Cauchy rows of this k (c_i = gf_inv(i ^ y), y = k + j: what Encoder emits
 // for a window aligned with the generation) decode by their repair index on
@@ -570,6 +597,14 @@ static int decoder_accept(qf_decoder* d, uint64_t id, int is_systematic, const u
     if (d->decoded || d->accepted >= d->k) return d->decoded ? 1 : 0;
     const uint32_t k = d->k;
     const uint32_t q = d->accepted;
+    if (!is_systematic && !coeffs) return QF_EINVAL;  // "Repair packet missing coefficients."
+    if (d->innovative) {
+        // the packet's vector over the k sources; dropped unless it is innovative
+        d->vec.assign(k, 0);
+        if (is_systematic) d->vec[id % k] = 1;
+        else memcpy(d->vec.data(), coeffs, coeff_len < k ? coeff_len : k);
+        if (!d->basis.add(d->vec.data())) return 0;
+    }
     if (is_systematic) {
         const uint32_t idx = (uint32_t)(id % k);  // decoder.rs:684
         if (d->sys_slot[idx] >= 0) return d->decoded ? 1 : 0;  // duplicate (687-691)

@@ -75,6 +75,22 @@ def cauchy_coefficients(k: int, r: int) -> bytes:
     return bytes(buf)[: k * r]
 
 
+def gf_rank(vectors, k: int) -> tuple[int, list[int]]:
+    """qf_gf256_rank (host, no device): `vectors` holds n vectors of k bytes
+    in arrival order (bytes-like, or anything bytes() accepts row by row, such
+    as an n x k uint8 array).  Returns (rank, flags): flags[s] = 1 iff vector
+    s is not in the GF(2^8) span of the vectors before it."""
+    raw = vectors.tobytes() if hasattr(vectors, "tobytes") else bytes(vectors)
+    if k <= 0 or len(raw) % k:
+        raise ValueError(f"gf_rank: {len(raw)} bytes are no whole number of vectors of k = {k} bytes")
+    n = len(raw) // k
+    buf = (ctypes.c_uint8 * max(1, len(raw))).from_buffer_copy(raw.ljust(max(1, len(raw)), b"\0"))
+    flags = (ctypes.c_uint8 * max(1, n))()
+    rank = ctypes.c_uint32(0)
+    check(L._lib().qf_gf256_rank(k, n, buf, flags, ctypes.byref(rank)), "gf_rank")
+    return int(rank.value), list(flags)[:n]
+
+
 # ---------------------------------------------------------------------------
 # Device context
 # ---------------------------------------------------------------------------
@@ -390,6 +406,66 @@ def recode_batch(rows, row_index, out, out_coeffs, status, k: int, m: int, Lb: i
         _ptr(out), _ptr(out_coeffs), _ptr(status)), "recode_batch")
 
 
+def rank_batch(row_index, rank, status, k: int, *, r: int = 0, max_rows: int, G: int, n_rows=None,
+               row_coeffs=None, innovative=None, ctx: Optional[Context] = None) -> None:
+    """qf_rank_batch: the rank of what each of G generations holds and,
+    optionally, which slots are innovative (innovative: [G, max_rows] bytes,
+    1 iff the slot's vector is not in the span of the slots before it).
+    Indices, n_rows and row_coeffs as decode_batch; no payload is read."""
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(rank, 4 * G, "rank")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if row_coeffs is not None:
+        _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    if innovative is not None:
+        _need(innovative, G * max_rows, "innovative")
+    ctx = ctx or default_context()
+    sh = L.RankShape(k, r, max_rows, 0)
+    check(L._lib().qf_rank_batch(
+        ctx.handle, ctypes.byref(sh), G, _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None,
+        _ptr(row_coeffs) if row_coeffs is not None else None,
+        _ptr(innovative) if innovative is not None else None,
+        _ptr(rank), _ptr(status)), "rank_batch")
+
+
+def decode_innovative_batch(rows, row_index, rec, rec_index, n_rec, status, k: int, r: int, Lb: int, *,
+                            max_rows: int, row_stride: int, rows_gen_stride: int, rec_row_stride: int,
+                            rec_gen_stride: int, G: int, n_rows=None, row_coeffs=None, rank=None,
+                            innovative=None, ctx: Optional[Context] = None) -> None:
+    """qf_decode_innovative_batch: decode_batch over the innovative slots only
+    (a row is accepted iff it raises the rank of the rows before it), for
+    recoded traffic whose first k rows may be dependent.  rank ([G] u32) and
+    innovative ([G, max_rows] bytes) are optional outputs, as rank_batch's."""
+    em = min(k, r)
+    _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, Lb), "rec")
+    _need(rec_index, 2 * G * em, "rec_index (min(k, r) entries per generation)")
+    _need(n_rec, 4 * G, "n_rec")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if row_coeffs is not None:
+        _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    if rank is not None:
+        _need(rank, 4 * G, "rank")
+    if innovative is not None:
+        _need(innovative, G * max_rows, "innovative")
+    ctx = ctx or default_context()
+    sh = L.DecodeShape(k, r, Lb, max_rows, row_stride, rows_gen_stride, rec_row_stride, rec_gen_stride)
+    check(L._lib().qf_decode_innovative_batch(
+        ctx.handle, ctypes.byref(sh), G, _ptr(rows), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None,
+        _ptr(row_coeffs) if row_coeffs is not None else None,
+        _ptr(rec) if rec is not None else None, _ptr(rec_index) if rec_index is not None else None,
+        _ptr(n_rec), _ptr(status),
+        _ptr(rank) if rank is not None else None,
+        _ptr(innovative) if innovative is not None else None), "decode_innovative_batch")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
@@ -545,16 +621,27 @@ class Encoder:
 class Decoder:
     """decoder.rs:658-791 Decoder (first k rows win, systematic id % k).
     k <= 256 decodes by Gauss-Jordan / the Cauchy kernels, k > 256 by the
-    Wiedemann strategy (decoder.rs:660-664, 794-975), as Decoder::new picks."""
+    Wiedemann strategy (decoder.rs:660-664, 794-975), as Decoder::new picks.
+    innovative_only=True (no reference counterpart, k <= 256): a packet is
+    taken only if it raises the rank of the packets taken before it, so
+    recoded traffic with dependent packets decodes once its rank reaches k."""
 
     def __init__(self, k: int, pool: Optional[MemoryPool] = None, max_len: int = 4096,
-                 ctx: Optional[Context] = None):
+                 ctx: Optional[Context] = None, innovative_only: bool = False):
         self.k = k
         self.ctx = ctx or default_context()
         self.max_len = pool.block_size if pool is not None else max_len
         h = ctypes.c_void_p()
         check(L._lib().qf_decoder_new(self.ctx.handle, k, self.max_len, ctypes.byref(h)), "Decoder::new")
         self.handle = h
+        self.innovative_only = bool(innovative_only)
+        if innovative_only:
+            check(L._lib().qf_decoder_set_innovative(self.handle, 1), "Decoder: innovative_only")
+
+    @property
+    def rank(self) -> int:
+        """Rank of the packets accepted so far (qf_decoder_rank)."""
+        return check(L._lib().qf_decoder_rank(self.handle), "Decoder.rank")
 
     @property
     def is_decoded(self) -> bool:
@@ -659,6 +746,24 @@ class Recoder:
         self._index[s: s + 1].fill_(index)
         self.count += 1
         self._len = max(self._len, len(data))
+
+    def rank(self) -> int:
+        """Rank of the rows held (rank_batch, G = 1): how many of them a
+        receiver can use, and the most independent packets recode can emit."""
+        import torch
+
+        if self.count == 0:
+            return 0
+        dev = self._rows.device
+        rank = torch.empty(1, dtype=torch.int32, device=dev)
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        n_rows = torch.full((1,), self.count, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(self.ctx.device).synchronize()
+        rank_batch(self._index, rank, status, self.k, max_rows=self.capacity, G=1, n_rows=n_rows,
+                   row_coeffs=self._coeffs, ctx=self.ctx)
+        self.ctx.sync()
+        check(int(status.cpu()[0]), "Recoder.rank")
+        return int(rank.cpu()[0])
 
     def recode(self, count: int, seed: int, first_id: int = 0) -> list:
         """`count` (1..64) recoded packets of the rows held, ids first_id ..;
