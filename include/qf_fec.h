@@ -763,6 +763,112 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
                         uint32_t *n_rows_dev, int32_t *frame_status_dev);
 
 /* ---------------------------------------------------------------------------
+ * Device framing of coded rows that carry their coefficient vectors: the wire
+ * step of a relay (qf_recode_batch) and of a receiver of recoded traffic
+ * (qf_decode_innovative_batch).  The two calls above frame and accept Cauchy
+ * repairs only.
+ *
+ * The payload-aligned layout: a frame slot is frame_stride bytes,
+ * frame_stride % 16 == 0 and >= P + L with P = qf_frame_payload_offset(k) =
+ * round_up(3 + k, 16).  The payload of every frame sits at byte P of its slot,
+ * whatever the frame's kind, and the frame's bytes (Packet::to_raw,
+ * encoder.rs:124-152) directly in front of it:
+ *   systematic  starts at slot byte P - 1:      0x01 | payload
+ *   coded       starts at slot byte P - 3 - k:  0x00 | k as BE u16 | k coefficient bytes | payload
+ * A sender transmits frame_len bytes starting at frame_off.  The payload
+ * position is 16-byte aligned and does not depend on the kind, so the payload
+ * kernels write straight into frame slots: qf_recode_batch with out_dev =
+ * frames_dev + P, out_row_stride = frame_stride and out_gen_stride = m *
+ * frame_stride, and framing then costs the header bytes only.
+ *
+ * Relay step, frames in and frames out, all on the device:
+ *   qf_parse_frames_coded_dev   frames -> rows, row_index, n_rows, row_coeffs
+ *   qf_recode_batch             m fresh rows per generation, written into the frame slots
+ *   qf_frame_rows_dev           QF_FRAME_IN_PLACE, row_index NULL, row_coeffs = out_coeffs_dev
+ * Receiver:
+ *   qf_parse_frames_coded_dev   then qf_decode_innovative_batch on its outputs
+ * The intermediate rows belong to the caller.
+ * ------------------------------------------------------------------------- */
+/* No reference counterpart (a layout rule): P = round_up(3 + k, 16) for k in
+ * 1..256, 0 otherwise.  Host only, no device. */
+uint32_t qf_frame_payload_offset(uint32_t k);
+
+#define QF_FRAME_IN_PLACE 1u   /* the payloads already sit at byte P of their slots */
+
+typedef struct qf_frame_rows_shape {
+    uint32_t k;              /* generation size, 1..256 */
+    uint32_t r;              /* Cauchy repairs that may appear when row_coeffs_dev is NULL */
+    uint32_t L;              /* payload bytes per row at most, >= 1 */
+    uint32_t max_rows;       /* slots per generation, 1..1024 */
+    uint32_t flags;          /* 0 or QF_FRAME_IN_PLACE */
+    uint32_t reserved;       /* 0 */
+    uint64_t row_stride;     /* inputs, as qf_decode_shape; not read in place */
+    uint64_t rows_gen_stride;
+    uint64_t frame_stride;   /* % 16 == 0, >= P + L */
+} qf_frame_rows_shape;
+
+/* Rows with index and vector -> frames (replaces Packet::to_raw,
+ * encoder.rs:124-152, per row of a batch; the batch itself has no reference
+ * counterpart).  rows_dev, row_index_dev, n_rows_dev (NULL: max_rows) and
+ * row_coeffs_dev (nullable) are laid out as for qf_decode_batch and
+ * qf_recode_batch; row_index_dev NULL means every row is coded, which with
+ * max_rows = m and row_coeffs_dev = out_coeffs_dev is the recoder's output.
+ * row_len_dev (nullable, one u32 per slot) is the payload bytes of the row;
+ * NULL means L.  Frame f = g*max_rows + s goes to frames_dev + f*frame_stride
+ * in the layout above; frame_len_dev[f] (required) and frame_off_dev[f]
+ * (nullable) receive its length and its start inside the slot.  The vector of
+ * a slot is v(s) of qf_recode_batch: index < k a systematic frame (no vector
+ * is read); index >= k the k bytes at (g*max_rows + s)*k of row_coeffs_dev,
+ * or without row_coeffs_dev Cauchy row index - k of (k, r).
+ * A slot gets frame_len = 0 (frame_off = 0) and no byte written when s >= n,
+ * when its row_len > L, or when its index >= k has neither a vector nor
+ * index - k < r.
+ * flags 0: the payload is copied from rows_dev to byte P of the slot (16-byte
+ * loads and stores).  QF_FRAME_IN_PLACE: the payloads already sit there,
+ * rows_dev is ignored (may be NULL) and only the header bytes are written.
+ * In both modes no byte of a slot outside [frame_off, frame_off + frame_len)
+ * is written.
+ * Returns QF_EINVAL for k outside 1..256, max_rows outside 1..1024, L == 0,
+ * unknown flags, reserved != 0, a NULL required pointer, pointers or strides
+ * not 16-byte aligned, a row stride shorter than L or frame_stride < P + L;
+ * QF_ERANGE for NULL row_coeffs_dev with r > 0 and k + r > 256.  G == 0 is
+ * QF_OK. */
+int qf_frame_rows_dev(qf_ctx *ctx, const qf_frame_rows_shape *shape, uint32_t G,
+                      const uint8_t *rows_dev, const uint16_t *row_index_dev,
+                      const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                      const uint32_t *row_len_dev, uint8_t *frames_dev,
+                      uint32_t *frame_len_dev, uint32_t *frame_off_dev);
+
+/* Received frames -> rows plus row_coeffs, the input of qf_recode_batch,
+ * qf_rank_batch and qf_decode_innovative_batch (Packet::from_raw,
+ * encoder.rs:18-68, then Decoder::add_packet's column rule, decoder.rs:684,
+ * which takes any coefficient vector, decoder.rs:694-696).  Arguments as
+ * qf_parse_frames_dev without r, plus:
+ *   frame_off_dev   (nullable) the start of frame s inside its slot, so the
+ *                   output of qf_frame_rows_dev parses directly; NULL means 0
+ *   row_coeffs_dev  (required) k bytes per output slot at (g*max_rows + slot)*k
+ *   row_len_dev     (nullable) the payload bytes of the row before zero padding
+ * A systematic frame gives row_index = id % k and the unit vector of that
+ * column, so row_coeffs_dev is fully defined.  A repair frame whose
+ * coefficient length is k is accepted whatever its vector (an all-zero vector
+ * is a legal row; the rank filter drops it): row_index = k and the k bytes
+ * are copied.  frame_status_dev: QF_OK; QF_EINVAL (empty, frame_off +
+ * frame_len > frame_stride, payload > L); QF_ETOOSMALL (coefficient length or
+ * coefficients truncated); QF_ERANGE (coefficient length other than k).
+ * Valid frames are compacted in arrival order and zero padded to L, with
+ * n_rows_dev[g] their count; output slots >= n_rows_dev[g] are not written.
+ * No byte outside [slot, slot + frame_stride) of a frame is read.
+ * k 1..256, max_rows 1..1024; alignment rules and call-level errors as
+ * qf_parse_frames_dev, with row_coeffs_dev among the required pointers. */
+int qf_parse_frames_coded_dev(qf_ctx *ctx, uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows,
+                              const uint8_t *frames_dev, uint64_t frame_stride,
+                              const uint32_t *frame_len_dev, const uint32_t *frame_off_dev,
+                              const uint64_t *ids_dev, const uint32_t *n_frames_dev,
+                              uint8_t *rows_dev, uint64_t row_stride, uint64_t rows_gen_stride,
+                              uint16_t *row_index_dev, uint32_t *n_rows_dev, uint8_t *row_coeffs_dev,
+                              uint32_t *row_len_dev, int32_t *frame_status_dev);
+
+/* ---------------------------------------------------------------------------
  * GF(2^16) "Extreme mode" codec.
  * replaces gf_tables.rs:331-380 (gf16_mul / gf16_pow / gf16_inv / gf16_mul_add)
  * and decoder.rs:10-88 (Encoder16), 536-656 (Decoder16).  Field mod 0x1100B

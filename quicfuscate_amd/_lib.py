@@ -75,6 +75,17 @@ class RankShape(ctypes.Structure):
     _fields_ = [("k", _U32), ("r", _U32), ("max_rows", _U32), ("flags", _U32)]
 
 
+class FrameRowsShape(ctypes.Structure):
+    """qf_frame_rows_shape (rows with index and vector -> payload-aligned frames)."""
+    _fields_ = [
+        ("k", _U32), ("r", _U32), ("L", _U32), ("max_rows", _U32), ("flags", _U32), ("reserved", _U32),
+        ("row_stride", _U64), ("rows_gen_stride", _U64), ("frame_stride", _U64),
+    ]
+
+
+QF_FRAME_IN_PLACE = 1   # qf_frame_rows_shape.flags: the payloads already sit in their frame slots
+
+
 class GenDesc(ctypes.Structure):
     """qf_gen_desc (heterogeneous encode batch)."""
     _fields_ = [
@@ -182,6 +193,10 @@ _SIGS = {
     "qf_frame_batch_dev": (_I, [_P, ctypes.POINTER(EncodeShape), _U32, _P, _P, _P, _U64, _P]),
     "qf_parse_frames_dev": (_I, [_P, _U32, _U32, _U32, _U32, _U32, _P, _U64, _P, _P, _P, _P, _U64, _U64, _P,
                                  _P, _P]),
+    "qf_frame_payload_offset": (_U32, [_U32]),
+    "qf_frame_rows_dev": (_I, [_P, ctypes.POINTER(FrameRowsShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_parse_frames_coded_dev": (_I, [_P, _U32, _U32, _U32, _U32, _P, _U64, _P, _P, _P, _P, _P, _U64, _U64, _P,
+                                       _P, _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

@@ -427,7 +427,7 @@ def build(verbose: bool = False) -> Path:
         futs = {
             s: ex.submit(_compile, s, build_dir,
                          ["-Rpass-analysis=kernel-resource-usage"]
-                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip")
+                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip", "qf_wire.hip")
                          else [])
             for s in SOURCES
         }
@@ -452,6 +452,16 @@ def build(verbose: bool = False) -> Path:
                 ru = _check_no_scratch(err)
                 if any(u.get("ScratchSize", 0) for u in ru.values()):
                     raise RuntimeError(f"k_rank_filter uses scratch: {ru}")
+                if verbose:
+                    for n, u in sorted(ru.items()):
+                        print(f"  {n}: {u}")
+            if s == "qf_wire.hip":
+                # the framing kernels of coded rows hold a few addresses and
+                # one 16-byte block per lane: no scratch
+                ru = _check_no_scratch(err)
+                new = {n: u for n, u in ru.items() if "k_frame_rows" in n or "k_parse_frames_coded" in n}
+                if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
+                    raise RuntimeError(f"k_frame_rows / k_parse_frames_coded missing or using scratch: {ru}")
                 if verbose:
                     for n, u in sorted(ru.items()):
                         print(f"  {n}: {u}")

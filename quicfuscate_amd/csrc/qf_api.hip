@@ -1097,6 +1097,16 @@ hipError_t launch_parse_frames(const uint8_t* frames, uint64_t frame_stride, con
                                uint32_t G, uint32_t max_rows, uint8_t* rows, uint64_t row_stride,
                                uint64_t rows_gen_stride, uint16_t* row_index, uint32_t* n_rows,
                                int32_t* frame_status, const uint8_t* explog, hipStream_t st);
+hipError_t launch_frame_rows(const uint8_t* rows, const uint16_t* row_index, const uint32_t* n_rows,
+                             const uint8_t* row_coeffs, const uint32_t* row_len, const qf_frame_rows_shape& sh,
+                             uint32_t G, uint8_t* frames, uint32_t* frame_len, uint32_t* frame_off,
+                             const uint8_t* explog, int num_cus, hipStream_t st);
+hipError_t launch_parse_frames_coded(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
+                                     const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
+                                     uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint8_t* rows,
+                                     uint64_t row_stride, uint64_t rows_gen_stride, uint16_t* row_index,
+                                     uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len,
+                                     int32_t* frame_status, hipStream_t st);
 }  // namespace qf
 
 extern "C" {
@@ -1769,6 +1779,59 @@ int qf_parse_frames_dev(qf_ctx* ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
                                          row_stride, rows_gen_stride, row_index, n_rows, frame_status,
                                          ctx->d_explog, ctx->stream));
     prof_end(ctx, ctx->stream, ev, "k_parse_frames");
+    return QF_OK;
+}
+
+uint32_t qf_frame_payload_offset(uint32_t k) { return k == 0 || k > 256 ? 0 : (3 + k + 15) / 16 * 16; }
+
+int qf_frame_rows_dev(qf_ctx* ctx, const qf_frame_rows_shape* sh, uint32_t G, const uint8_t* rows,
+                      const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                      const uint32_t* row_len, uint8_t* frames, uint32_t* frame_len, uint32_t* frame_off) {
+    if (!ctx || !sh) return QF_EINVAL;
+    const uint32_t k = sh->k, r = sh->r, L = sh->L;
+    const bool in_place = (sh->flags & QF_FRAME_IN_PLACE) != 0;
+    if (k == 0 || k > 256 || sh->max_rows == 0 || sh->max_rows > 1024 || L == 0) return QF_EINVAL;
+    if ((sh->flags & ~QF_FRAME_IN_PLACE) || sh->reserved) return QF_EINVAL;
+    if (!row_coeffs && r && k + r > 256) return QF_ERANGE;
+    if (G == 0) return QF_OK;
+    if (!frames || !frame_len || (!in_place && !rows)) return QF_EINVAL;
+    if ((sh->frame_stride & 15) || !aligned16(frames) ||
+        sh->frame_stride < (uint64_t)qf_frame_payload_offset(k) + L)
+        return QF_EINVAL;
+    if (!in_place && (!aligned16(rows) || (sh->row_stride & 15) || (sh->rows_gen_stride & 15) || sh->row_stride < L))
+        return QF_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    int s = ensure_device(ctx);
+    if (s) return s;
+    hipEvent_t ev = prof_begin(ctx, ctx->stream);
+    QF_CHECK_HIP(qf::launch_frame_rows(in_place ? nullptr : rows, row_index, n_rows, row_coeffs, row_len, *sh, G,
+                                       frames, frame_len, frame_off, ctx->d_explog, ctx->num_cus, ctx->stream));
+    prof_end(ctx, ctx->stream, ev, "k_frame_rows");
+    return QF_OK;
+}
+
+int qf_parse_frames_coded_dev(qf_ctx* ctx, uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows,
+                              const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
+                              const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
+                              uint8_t* rows, uint64_t row_stride, uint64_t rows_gen_stride, uint16_t* row_index,
+                              uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len, int32_t* frame_status) {
+    if (!ctx) return QF_EINVAL;
+    if (k == 0 || k > 256) return QF_EINVAL;
+    if (G == 0) return QF_OK;
+    if (max_rows == 0 || max_rows > 1024 || L == 0) return QF_EINVAL;
+    if (!frames || !frame_len || !ids || !rows || !row_index || !n_rows || !row_coeffs || !frame_status)
+        return QF_EINVAL;
+    if ((frame_stride & 15) || !aligned16(frames) || !aligned16(rows) || (row_stride & 15) ||
+        (rows_gen_stride & 15) || row_stride < L)
+        return QF_EINVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    int s = ensure_device(ctx);
+    if (s) return s;
+    hipEvent_t ev = prof_begin(ctx, ctx->stream);
+    QF_CHECK_HIP(qf::launch_parse_frames_coded(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
+                                               max_rows, rows, row_stride, rows_gen_stride, row_index, n_rows,
+                                               row_coeffs, row_len, frame_status, ctx->stream));
+    prof_end(ctx, ctx->stream, ev, "k_parse_frames_coded");
     return QF_OK;
 }
 

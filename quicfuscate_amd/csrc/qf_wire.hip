@@ -4,6 +4,10 @@
 //   k_frame_batch   encode batch -> frames: source i "0x01 | payload",
 //                   repair j "0x00 | k (BE u16) | C[j][0..k) | payload"
 //   k_parse_frames  received frames -> decode-batch rows / row_index / n_rows
+//   k_frame_rows          rows with index and vector -> frames in payload-aligned
+//                         slots (any coefficient vector)
+//   k_parse_frames_coded  frames at an offset in their slots -> rows / row_index /
+//                         n_rows / row_coeffs / row_len, any coefficient vector
 //
 // Payloads sit at byte offset 1 or 3 + k inside a frame, so the copy loops
 // move 16-byte blocks assembled from aligned dwords with v_alignbit (one
@@ -208,9 +212,322 @@ __global__ void __launch_bounds__(256) k_parse_frames(ParseArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Coded rows that carry their coefficient vectors (relay and receiver of
+// recoded traffic).  Payload-aligned slots: the payload of every frame sits at
+// byte P = round_up(3 + k, 16) of its slot and the frame's header directly in
+// front of it, so payload copies are aligned 16-byte loads and stores.
+// ---------------------------------------------------------------------------
+
+// 16 bytes from slot byte o (any alignment) of a frame whose readable bytes end
+// at slot byte `end`: one aligned 16-byte load, else aligned dwords joined with
+// v_alignbit (which touch up to 3 bytes past o + 16, hence the 20).  The
+// caller has checked can_copy16(o, end).
+QF_DEV bool can_copy16(uint32_t o, uint32_t end) {
+    return (o & 15) == 0 ? o + 16 <= end : o + 20 <= end;
+}
+
+QF_DEV uint4 load16(const uint8_t* slot, uint32_t o) {
+    if ((o & 15) == 0) return *reinterpret_cast<const uint4*>(slot + o);
+    uint4 v;
+    v.x = load_u32_unaligned(slot, o);
+    v.y = load_u32_unaligned(slot, o + 4);
+    v.z = load_u32_unaligned(slot, o + 8);
+    v.w = load_u32_unaligned(slot, o + 12);
+    return v;
+}
+
+struct FrameRowsArgs {
+    const uint8_t* rows;        // NULL in place
+    const uint16_t* row_index;  // NULL: every row coded
+    const uint32_t* n_rows;     // NULL: max_rows
+    const uint8_t* row_coeffs;  // NULL: Cauchy rows of (k, r)
+    const uint32_t* row_len;    // NULL: L
+    uint8_t* frames;
+    uint32_t* frame_len;
+    uint32_t* frame_off;        // may be NULL
+    const uint8_t* explog;
+    uint64_t row_stride, rows_gen_stride, frame_stride;
+    uint32_t k, r, L, max_rows, P;
+    uint32_t hdr_blocks;        // P / 16
+    uint32_t blocks_per_frame;  // hdr_blocks (+ ceil(L / 16) in copy mode)
+    uint64_t total_blocks;
+};
+
+// one lane per 16-byte block of a slot: blocks [0, P/16) hold the header,
+// the blocks behind them the payload (copy mode only)
+__global__ void __launch_bounds__(256) k_frame_rows(FrameRowsArgs a) {
+    __shared__ uint8_t sexp[512];
+    __shared__ uint8_t slog[256];
+    if (!a.row_coeffs) {
+        for (uint32_t i = threadIdx.x; i < 768; i += blockDim.x) {
+            if (i < 512) sexp[i] = a.explog[i];
+            else slog[i - 512] = a.explog[i];
+        }
+    }
+    __syncthreads();
+    for (uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; b < a.total_blocks;
+         b += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t f = b / a.blocks_per_frame;
+        const uint32_t blk = (uint32_t)(b - f * a.blocks_per_frame);
+        const uint64_t g = f / a.max_rows;
+        const uint32_t s = (uint32_t)(f - g * a.max_rows);
+        const uint32_t n = a.n_rows ? min(a.n_rows[g], a.max_rows) : a.max_rows;
+        const uint32_t idx = a.row_index ? a.row_index[f] : a.k;
+        const uint32_t rlen = a.row_len ? a.row_len[f] : a.L;
+        const bool sys = idx < a.k;
+        const bool valid = s < n && rlen <= a.L && (sys || a.row_coeffs || idx - a.k < a.r);
+        const uint32_t foff = sys ? a.P - 1 : a.P - 3 - a.k;
+        if (blk == 0) {
+            a.frame_len[f] = valid ? a.P - foff + rlen : 0;
+            if (a.frame_off) a.frame_off[f] = valid ? foff : 0;
+        }
+        if (!valid) continue;
+        uint8_t* slot = a.frames + f * a.frame_stride;
+        const uint32_t t0 = blk * 16;
+        if (blk >= a.hdr_blocks) {
+            // payload block: both sides 16-byte aligned
+            const uint32_t p0 = t0 - a.P;
+            if (p0 >= rlen) continue;
+            const uint8_t* row = a.rows + g * a.rows_gen_stride + (uint64_t)s * a.row_stride;
+            if (p0 + 16 <= rlen) {
+                *reinterpret_cast<uint4*>(slot + t0) = *reinterpret_cast<const uint4*>(row + p0);
+            } else {
+                for (uint32_t t = p0; t < rlen; ++t) slot[a.P + t] = row[t];
+            }
+            continue;
+        }
+        if (t0 + 16 <= foff) continue;   // in front of the frame
+        if (sys) {
+            slot[foff] = 1;
+            continue;
+        }
+        // header of a coded frame: 0x00 | k (BE u16) | vector
+        const uint32_t v0 = foff + 3;    // slot byte of the vector
+        const uint8_t* vec = a.row_coeffs ? a.row_coeffs + f * a.k : nullptr;
+        if (vec && t0 >= v0 && ((uintptr_t)(vec + (t0 - v0)) & 15) == 0) {
+            // P - v0 = k: the block ends inside the vector; 16 aligned bytes of it
+            *reinterpret_cast<uint4*>(slot + t0) = *reinterpret_cast<const uint4*>(vec + (t0 - v0));
+            continue;
+        }
+        for (uint32_t t = max(t0, foff); t < t0 + 16; ++t) {
+            const uint32_t h = t - foff;
+            uint8_t v;
+            if (h == 0) v = 0;
+            else if (h == 1) v = (uint8_t)(a.k >> 8);
+            else if (h == 2) v = (uint8_t)(a.k & 0xFF);
+            else v = vec ? vec[h - 3] : cauchy_coeff(sexp, slog, h - 3, a.k, idx - a.k);
+            slot[t] = v;
+        }
+    }
+}
+
+struct ParseCodedArgs {
+    const uint8_t* frames;
+    uint64_t frame_stride;
+    const uint32_t* frame_len;
+    const uint32_t* frame_off;  // NULL: 0
+    const uint64_t* ids;
+    const uint32_t* n_frames;
+    uint8_t* rows;
+    uint64_t row_stride, rows_gen_stride;
+    uint16_t* row_index;
+    uint32_t* n_rows;
+    uint8_t* row_coeffs;
+    uint32_t* row_len;          // may be NULL
+    int32_t* frame_status;
+    uint32_t k, L, max_rows;
+};
+
+// one 256-thread block per generation; k_parse_frames with any coefficient
+// vector accepted and written out, and frames at an offset inside their slots
+__global__ void __launch_bounds__(256) k_parse_frames_coded(ParseCodedArgs a) {
+    __shared__ uint32_t slot_of[1024];   // frame -> output slot (or ~0)
+    __shared__ uint32_t pay_of[1024];    // payload start, from the slot's first byte
+    __shared__ uint32_t len_of[1024];    // payload length
+    __shared__ uint16_t idx_of[1024];    // column of a systematic frame, k for a coded one
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t g = blockIdx.x;
+    const uint32_t nf = a.n_frames ? min(a.n_frames[g], a.max_rows) : a.max_rows;
+    uint32_t base = 0;
+    for (uint32_t s0 = 0; s0 < nf; s0 += blockDim.x) {
+        const uint32_t s = s0 + threadIdx.x;
+        int32_t st = QF_OK;
+        uint32_t idx = 0xFFFF, pay = 0, plen = 0;
+        if (s < nf) {
+            const uint64_t fi = (uint64_t)g * a.max_rows + s;
+            const uint32_t flen = a.frame_len[fi];
+            const uint32_t foff = a.frame_off ? a.frame_off[fi] : 0;
+            const uint8_t* fr = a.frames + fi * a.frame_stride + foff;
+            uint32_t off = 0;
+            if (flen == 0 || (uint64_t)foff + flen > a.frame_stride) {
+                st = QF_EINVAL;  // "Raw data is empty", or not inside its slot
+            } else if (fr[0] == 1) {
+                off = 1;
+                idx = (uint32_t)(a.ids[fi] % a.k);  // decoder.rs:684
+            } else if (flen < 3) {
+                st = QF_ETOOSMALL;  // coefficient length missing (encoder.rs:33-38)
+            } else {
+                const uint32_t cl = ((uint32_t)fr[1] << 8) | fr[2];
+                if (flen < 3 + cl) st = QF_ETOOSMALL;  // coefficients truncated
+                else if (cl != a.k) st = QF_ERANGE;
+                off = 3 + cl;
+                idx = a.k;
+            }
+            if (st == QF_OK) {
+                plen = flen - off;
+                pay = foff + off;
+                if (plen > a.L) st = QF_EINVAL;
+            }
+            a.frame_status[fi] = st;
+        }
+        const bool ok = s < nf && st == QF_OK;
+        // block-wide exclusive prefix of ok (4 waves)
+        const uint64_t bal = __ballot(ok);
+        const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const uint32_t before = __popcll(bal & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
+        if (lane == 0) wave_cnt[w] = __popcll(bal);
+        __syncthreads();
+        uint32_t woff = 0;
+        for (uint32_t q = 0; q < w; ++q) woff += wave_cnt[q];
+        uint32_t total = 0;
+        for (uint32_t q = 0; q < 4; ++q) total += wave_cnt[q];
+        if (s < nf) {   // nf <= max_rows <= 1024
+            slot_of[s] = ok ? base + woff + before : 0xFFFFFFFFu;
+            pay_of[s] = pay;
+            len_of[s] = plen;
+            idx_of[s] = (uint16_t)idx;
+        }
+        if (ok) {
+            const uint64_t o = (uint64_t)g * a.max_rows + base + woff + before;
+            a.row_index[o] = (uint16_t)idx;
+            if (a.row_len) a.row_len[o] = plen;
+        }
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.n_rows[g] = base;
+    __syncthreads();
+    // 16-byte blocks of every accepted row: the payload, zero beyond it, then
+    // the coefficient vector (the unit vector of a systematic frame)
+    const uint32_t bpr = (a.L + 15) / 16, cpr = (a.k + 15) / 16, upr = bpr + cpr;
+    const uint32_t nwork = nf * upr;
+    for (uint32_t w = threadIdx.x; w < nwork; w += blockDim.x) {
+        const uint32_t s = w / upr, u = w - s * upr;
+        const uint32_t slot = slot_of[s];
+        if (slot == 0xFFFFFFFFu) continue;
+        const uint64_t fi = (uint64_t)g * a.max_rows + s;
+        const uint8_t* fslot = a.frames + fi * a.frame_stride;
+        const uint32_t pay = pay_of[s], plen = len_of[s];
+        if (u < bpr) {
+            uint8_t* dst = a.rows + g * a.rows_gen_stride + (uint64_t)slot * a.row_stride;
+            const uint32_t t0 = u * 16;
+            if (t0 + 16 <= plen && can_copy16(pay + t0, pay + plen)) {
+                *reinterpret_cast<uint4*>(dst + t0) = load16(fslot, pay + t0);
+            } else if (t0 >= plen && t0 + 16 <= a.L) {
+                *reinterpret_cast<uint4*>(dst + t0) = make_uint4(0, 0, 0, 0);
+            } else {
+                for (uint32_t t = t0; t < t0 + 16 && t < a.L; ++t) dst[t] = t < plen ? fslot[pay + t] : 0;
+            }
+            continue;
+        }
+        const uint32_t c0 = (u - bpr) * 16;
+        const uint32_t cend = min(c0 + 16, a.k);
+        uint8_t* cd = a.row_coeffs + ((uint64_t)g * a.max_rows + slot) * a.k;
+        const uint32_t idx = idx_of[s];
+        const bool wide = c0 + 16 <= a.k && ((uintptr_t)(cd + c0) & 15) == 0;
+        if (idx < a.k) {
+            if (wide) {
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (idx >= c0 && idx < c0 + 16) {
+                    const uint32_t bit = 1u << (8 * (idx & 3));
+                    const uint32_t q = (idx - c0) >> 2;
+                    v.x = q == 0 ? bit : 0;
+                    v.y = q == 1 ? bit : 0;
+                    v.z = q == 2 ? bit : 0;
+                    v.w = q == 3 ? bit : 0;
+                }
+                *reinterpret_cast<uint4*>(cd + c0) = v;
+            } else {
+                for (uint32_t t = c0; t < cend; ++t) cd[t] = t == idx ? 1 : 0;
+            }
+            continue;
+        }
+        // the vector sits in front of the payload: bytes [pay - k, pay) of the slot
+        const uint32_t v0 = pay - a.k;
+        if (wide && can_copy16(v0 + c0, pay + plen)) {
+            *reinterpret_cast<uint4*>(cd + c0) = load16(fslot, v0 + c0);
+        } else {
+            for (uint32_t t = c0; t < cend; ++t) cd[t] = fslot[v0 + t];
+        }
+    }
+}
+
 }  // namespace
 
 namespace qf {
+
+hipError_t launch_frame_rows(const uint8_t* rows, const uint16_t* row_index, const uint32_t* n_rows,
+                             const uint8_t* row_coeffs, const uint32_t* row_len, const qf_frame_rows_shape& sh,
+                             uint32_t G, uint8_t* frames, uint32_t* frame_len, uint32_t* frame_off,
+                             const uint8_t* explog, int num_cus, hipStream_t st) {
+    FrameRowsArgs a{};
+    a.rows = rows;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.row_coeffs = row_coeffs;
+    a.row_len = row_len;
+    a.frames = frames;
+    a.frame_len = frame_len;
+    a.frame_off = frame_off;
+    a.explog = explog;
+    a.row_stride = sh.row_stride;
+    a.rows_gen_stride = sh.rows_gen_stride;
+    a.frame_stride = sh.frame_stride;
+    a.k = sh.k;
+    a.r = sh.r;
+    a.L = sh.L;
+    a.max_rows = sh.max_rows;
+    a.P = qf_frame_payload_offset(sh.k);
+    a.hdr_blocks = a.P / 16;
+    a.blocks_per_frame = a.hdr_blocks + ((sh.flags & QF_FRAME_IN_PLACE) ? 0 : (sh.L + 15) / 16);
+    a.total_blocks = (uint64_t)G * sh.max_rows * a.blocks_per_frame;
+    if (a.total_blocks == 0) return hipSuccess;
+    uint64_t blocks = (a.total_blocks + 255) / 256;
+    const uint64_t cap = (uint64_t)num_cus * 8;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(k_frame_rows, dim3((uint32_t)blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_parse_frames_coded(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
+                                     const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
+                                     uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint8_t* rows,
+                                     uint64_t row_stride, uint64_t rows_gen_stride, uint16_t* row_index,
+                                     uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len,
+                                     int32_t* frame_status, hipStream_t st) {
+    ParseCodedArgs a{};
+    a.frames = frames;
+    a.frame_stride = frame_stride;
+    a.frame_len = frame_len;
+    a.frame_off = frame_off;
+    a.ids = ids;
+    a.n_frames = n_frames;
+    a.rows = rows;
+    a.row_stride = row_stride;
+    a.rows_gen_stride = rows_gen_stride;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.row_coeffs = row_coeffs;
+    a.row_len = row_len;
+    a.frame_status = frame_status;
+    a.k = k;
+    a.L = L;
+    a.max_rows = max_rows;
+    if (G == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_parse_frames_coded, dim3(G), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_frame_batch(const uint8_t* src, const uint8_t* rep, const qf_encode_shape& sh, uint32_t G,
                               uint8_t* frames, uint64_t frame_stride, uint32_t* frame_len,

@@ -36,6 +36,7 @@ __all__ = [
     "QfError", "Context", "default_context", "init_gf_tables", "gf_mul", "gf_mul_table",
     "gf_mul_add", "gf_inv", "gf_mul_slice", "cauchy_coefficients", "MemoryPool", "Packet",
     "Encoder", "Decoder", "encode_batch", "decode_batch", "recode_batch", "Recoder",
+    "frame_payload_offset", "frame_rows", "parse_frames_coded",
     "gf16_mul", "gf16_inv", "cauchy16_coefficients", "encode16_batch", "decode16_batch", "Encoder16", "Decoder16",
 ]
 
@@ -464,6 +465,83 @@ def decode_innovative_batch(rows, row_index, rec, rec_index, n_rec, status, k: i
         _ptr(n_rec), _ptr(status),
         _ptr(rank) if rank is not None else None,
         _ptr(innovative) if innovative is not None else None), "decode_innovative_batch")
+
+
+def frame_payload_offset(k: int) -> int:
+    """qf_frame_payload_offset: byte P = round_up(3 + k, 16) of a frame slot at
+    which every payload sits in the payload-aligned layout (0 for k outside
+    1..256).  Host only."""
+    return int(L._lib().qf_frame_payload_offset(int(k) & 0xFFFFFFFF))
+
+
+def frame_rows(rows, frames, frame_len, k: int, Lb: int, *, r: int = 0, max_rows: int, row_stride: int = 0,
+               rows_gen_stride: int = 0, frame_stride: int, G: int, row_index=None, n_rows=None, row_coeffs=None,
+               row_len=None, frame_off=None, in_place: bool = False, ctx: Optional[Context] = None) -> None:
+    """qf_frame_rows_dev: rows with index and vector -> frames in the
+    payload-aligned layout (frame f = g*max_rows + s at frames + f*frame_stride,
+    its bytes at [frame_off[f], frame_off[f] + frame_len[f])).  Inputs as
+    recode_batch; row_index None: every row coded (the recoder's output with
+    row_coeffs = its out_coeffs).  in_place: the payloads already sit at byte
+    frame_payload_offset(k) of their slots, rows may be None and only the
+    headers are written."""
+    P = frame_payload_offset(k)
+    if not in_place:
+        _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
+    _need(frames, _span(G * max_rows, frame_stride, 1, 0, P + Lb), "frames")
+    _need(frame_len, 4 * G * max_rows, "frame_len")
+    if frame_off is not None:
+        _need(frame_off, 4 * G * max_rows, "frame_off")
+    if row_index is not None:
+        _need(row_index, 2 * G * max_rows, "row_index")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if row_coeffs is not None:
+        _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    if row_len is not None:
+        _need(row_len, 4 * G * max_rows, "row_len")
+    ctx = ctx or default_context()
+    sh = L.FrameRowsShape(k, r, Lb, max_rows, L.QF_FRAME_IN_PLACE if in_place else 0, 0, row_stride, rows_gen_stride,
+                          frame_stride)
+    check(L._lib().qf_frame_rows_dev(
+        ctx.handle, ctypes.byref(sh), G, _ptr(rows) if (rows is not None and not in_place) else None,
+        _ptr(row_index) if row_index is not None else None,
+        _ptr(n_rows) if n_rows is not None else None,
+        _ptr(row_coeffs) if row_coeffs is not None else None,
+        _ptr(row_len) if row_len is not None else None,
+        _ptr(frames), _ptr(frame_len),
+        _ptr(frame_off) if frame_off is not None else None), "frame_rows")
+
+
+def parse_frames_coded(frames, frame_len, ids, rows, row_index, n_rows, frame_status, row_coeffs, k: int, Lb: int, *,
+                       max_rows: int, frame_stride: int, row_stride: int, rows_gen_stride: int, G: int,
+                       n_frames=None, frame_off=None, row_len=None, ctx: Optional[Context] = None) -> None:
+    """qf_parse_frames_coded_dev: received frames -> rows, row_index, n_rows and
+    row_coeffs ([G, max_rows, k] bytes: the frame's vector, or the unit vector
+    of a systematic frame), the inputs of recode_batch, rank_batch and
+    decode_innovative_batch.  Any coefficient vector of length k is accepted.
+    frame_off: where each frame starts inside its slot (frame_rows' output);
+    row_len: optional output, the payload bytes before zero padding."""
+    _need(frames, G * max_rows * frame_stride, "frames")
+    _need(frame_len, 4 * G * max_rows, "frame_len")
+    _need(ids, 8 * G * max_rows, "ids")
+    _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(n_rows, 4 * G, "n_rows")
+    _need(frame_status, 4 * G * max_rows, "frame_status")
+    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    if n_frames is not None:
+        _need(n_frames, 4 * G, "n_frames")
+    if frame_off is not None:
+        _need(frame_off, 4 * G * max_rows, "frame_off")
+    if row_len is not None:
+        _need(row_len, 4 * G * max_rows, "row_len")
+    ctx = ctx or default_context()
+    check(L._lib().qf_parse_frames_coded_dev(
+        ctx.handle, k, Lb, G, max_rows, _ptr(frames), frame_stride, _ptr(frame_len),
+        _ptr(frame_off) if frame_off is not None else None, _ptr(ids),
+        _ptr(n_frames) if n_frames is not None else None,
+        _ptr(rows), row_stride, rows_gen_stride, _ptr(row_index), _ptr(n_rows), _ptr(row_coeffs),
+        _ptr(row_len) if row_len is not None else None, _ptr(frame_status)), "parse_frames_coded")
 
 
 # ---------------------------------------------------------------------------
