@@ -389,6 +389,61 @@ int qf_recode_batch(qf_ctx *ctx, const qf_recode_shape *shape, uint32_t G,
                     uint8_t *out_dev, uint8_t *out_coeffs_dev, int32_t *status_dev);
 
 /* ---------------------------------------------------------------------------
+ * Recoding from rows that lie where they were received (relay, in place).
+ * No reference counterpart.  qf_recode_batch with r = 0 over rows given as
+ * (where, how long) instead of a strided array:
+ *   rows[g][c] = the row_len_dev[g*max_rows + c] bytes at
+ *                src_dev + g*src_gen_stride + row_off_dev[g*max_rows + c],
+ *                zero padded to L
+ * which is what qf_parse_frame_headers_dev leaves of a batch of received
+ * frames (src_dev = frames_dev, src_gen_stride = max_rows * frame_stride).
+ * row_index_dev, n_rows_dev (NULL: max_rows), row_coeffs_dev (required here),
+ * mix_dev / seed (the splitmix stream indexed by the compacted slot), out_dev,
+ * out_coeffs_dev, the QF_ENOTREADY / QF_EINVAL cases of status_dev and the
+ * all-zero outputs of a generation that is not QF_OK are those of
+ * qf_recode_batch, and the outputs are byte for byte what qf_recode_batch
+ * writes for the rows defined above.
+ * Further QF_EINVAL cases of status_dev[g] (zero outputs): one of the
+ * generation's n rows has row_len > L, row_off % 16 != 0 or row_off + row_len
+ * > src_gen_stride.  row_len == 0 is legal: the row contributes its vector
+ * only.
+ * out_len_dev (nullable), one u32 per output slot at g*m + j: the largest
+ * row_len among the generation's n rows, 0 for a generation that is not
+ * QF_OK -- the row_len_dev of qf_frame_rows_dev for the recoded rows.
+ * Reads: only aligned 16-byte units of a source row that hold at least one of
+ * its bytes; with the offsets and src_gen_stride multiples of 16 they lie
+ * inside the generation's region.  Writes: exactly L bytes per output row.
+ * src_dev is never written and must not overlap out_dev.
+ * Returns QF_EINVAL for k or max_rows outside 1..255, m outside 1..64, L == 0,
+ * flags or reserved != 0, out_row_stride < L, a NULL required pointer
+ * (src_dev, row_off_dev, row_len_dev, row_index_dev, row_coeffs_dev, out_dev,
+ * out_coeffs_dev, status_dev), src_dev, out_dev or a stride not 16-byte
+ * aligned.  G == 0 is QF_OK.
+ * The payload runs ceil(m / 16) passes of k_combine_rows_at, whatever the row
+ * length (the generated bit-sliced payload kernels are not used); each pass
+ * reads every input row once.
+ * ------------------------------------------------------------------------- */
+typedef struct qf_recode_frames_shape {
+    uint32_t k;              /* generation size, 1..255 */
+    uint32_t L;              /* payload bytes per output row, >= every row_len, >= 1 */
+    uint32_t max_rows;       /* input slots per generation, 1..255 */
+    uint32_t m;              /* recoded packets per generation, 1..64 */
+    uint32_t flags;          /* 0 */
+    uint32_t reserved;       /* 0 */
+    uint64_t src_gen_stride; /* bytes of one generation's source region, % 16 == 0 */
+    uint64_t out_row_stride;
+    uint64_t out_gen_stride;
+} qf_recode_frames_shape;
+
+int qf_recode_frames_dev(qf_ctx *ctx, const qf_recode_frames_shape *shape, uint32_t G,
+                         const uint8_t *src_dev, const uint32_t *row_off_dev,
+                         const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                         const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                         const uint8_t *mix_dev, uint64_t seed,
+                         uint8_t *out_dev, uint8_t *out_coeffs_dev, uint32_t *out_len_dev,
+                         int32_t *status_dev);
+
+/* ---------------------------------------------------------------------------
  * Rank-aware receive side for recoded traffic (opt-in extension).
  * No reference counterpart: the reference's Cauchy code makes any k distinct
  * rows independent, so its decoder takes the first k rows (decoder.rs:678-701)
@@ -785,6 +840,12 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
  *   qf_parse_frames_coded_dev   frames -> rows, row_index, n_rows, row_coeffs
  *   qf_recode_batch             m fresh rows per generation, written into the frame slots
  *   qf_frame_rows_dev           QF_FRAME_IN_PLACE, row_index NULL, row_coeffs = out_coeffs_dev
+ * The same step without the copy of the payloads out of their slots (the
+ * received frames in this layout, so every payload starts at a multiple of 16):
+ *   qf_parse_frame_headers_dev  frames -> row_off, row_len, row_index, n_rows, row_coeffs
+ *   qf_recode_frames_dev        src_dev = frames_in, src_gen_stride = max_rows * frame_stride,
+ *                               out_dev = frames_out + P; out_len_dev = the rows' lengths
+ *   qf_frame_rows_dev           QF_FRAME_IN_PLACE, row_len_dev = out_len_dev
  * Receiver:
  *   qf_parse_frames_coded_dev   then qf_decode_innovative_batch on its outputs
  * The intermediate rows belong to the caller.
@@ -867,6 +928,35 @@ int qf_parse_frames_coded_dev(qf_ctx *ctx, uint32_t k, uint32_t L, uint32_t G, u
                               uint8_t *rows_dev, uint64_t row_stride, uint64_t rows_gen_stride,
                               uint16_t *row_index_dev, uint32_t *n_rows_dev, uint8_t *row_coeffs_dev,
                               uint32_t *row_len_dev, int32_t *frame_status_dev);
+
+/* qf_parse_frames_coded_dev that reads the headers only and leaves every
+ * payload in its slot, for qf_recode_frames_dev.  No reference counterpart
+ * beyond that call's.  Arguments as qf_parse_frames_coded_dev without
+ * rows_dev, row_stride and rows_gen_stride, with row_len_dev required, plus:
+ *   row_off_dev  (required) one u32 per output slot at g*max_rows + c: the
+ *                byte offset of compacted row c's payload from the start of
+ *                generation g's frame region, frames_dev + g*max_rows*
+ *                frame_stride; that is slot*frame_stride + frame_off + 1 for a
+ *                systematic frame and + 3 + k for a coded one
+ * row_index_dev, n_rows_dev, row_coeffs_dev, row_len_dev and frame_status_dev
+ * receive exactly what qf_parse_frames_coded_dev writes for the same frames
+ * (valid frames compacted in arrival order, output slots >= n_rows_dev[g] not
+ * written), with one more per-frame status: a frame that is otherwise valid
+ * but whose payload does not start at a multiple of 16 in its slot is
+ * QF_EINVAL and is not compacted (never the case in the payload-aligned
+ * layout).
+ * No payload byte is read: at most the 3 header bytes and the k vector bytes
+ * of a frame, all inside [slot, slot + frame_stride).
+ * k 1..256, max_rows 1..1024; alignment rules and call-level errors as
+ * qf_parse_frames_coded_dev, with row_len_dev and row_off_dev among the
+ * required pointers, and QF_EINVAL when max_rows * frame_stride > 2^32 (the
+ * offsets are u32). */
+int qf_parse_frame_headers_dev(qf_ctx *ctx, uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows,
+                               const uint8_t *frames_dev, uint64_t frame_stride,
+                               const uint32_t *frame_len_dev, const uint32_t *frame_off_dev,
+                               const uint64_t *ids_dev, const uint32_t *n_frames_dev,
+                               uint16_t *row_index_dev, uint32_t *n_rows_dev, uint8_t *row_coeffs_dev,
+                               uint32_t *row_len_dev, uint32_t *row_off_dev, int32_t *frame_status_dev);
 
 /* ---------------------------------------------------------------------------
  * GF(2^16) "Extreme mode" codec.

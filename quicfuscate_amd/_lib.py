@@ -70,6 +70,14 @@ class RecodeShape(ctypes.Structure):
     ]
 
 
+class RecodeFramesShape(ctypes.Structure):
+    """qf_recode_frames_shape (recoding from rows given as offset and length)."""
+    _fields_ = [
+        ("k", _U32), ("L", _U32), ("max_rows", _U32), ("m", _U32), ("flags", _U32), ("reserved", _U32),
+        ("src_gen_stride", _U64), ("out_row_stride", _U64), ("out_gen_stride", _U64),
+    ]
+
+
 class RankShape(ctypes.Structure):
     """qf_rank_shape (innovative-row filter)."""
     _fields_ = [("k", _U32), ("r", _U32), ("max_rows", _U32), ("flags", _U32)]
@@ -197,6 +205,10 @@ _SIGS = {
     "qf_frame_rows_dev": (_I, [_P, ctypes.POINTER(FrameRowsShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_parse_frames_coded_dev": (_I, [_P, _U32, _U32, _U32, _U32, _P, _U64, _P, _P, _P, _P, _P, _U64, _U64, _P,
                                        _P, _P, _P, _P]),
+    "qf_parse_frame_headers_dev": (_I, [_P, _U32, _U32, _U32, _U32, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _P]),
+    "qf_recode_frames_dev": (_I, [_P, ctypes.POINTER(RecodeFramesShape), _U32, _P, _P, _P, _P, _P, _P, _P, _U64,
+                                  _P, _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

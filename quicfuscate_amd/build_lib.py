@@ -29,7 +29,7 @@ LIB = OUT_DIR / "libqf_fec.so"
 LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
-           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip"]
+           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -427,7 +427,8 @@ def build(verbose: bool = False) -> Path:
         futs = {
             s: ex.submit(_compile, s, build_dir,
                          ["-Rpass-analysis=kernel-resource-usage"]
-                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip", "qf_wire.hip")
+                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip", "qf_wire.hip",
+                                  "qf_relay.hip")
                          else [])
             for s in SOURCES
         }
@@ -459,9 +460,22 @@ def build(verbose: bool = False) -> Path:
                 # the framing kernels of coded rows hold a few addresses and
                 # one 16-byte block per lane: no scratch
                 ru = _check_no_scratch(err)
-                new = {n: u for n, u in ru.items() if "k_frame_rows" in n or "k_parse_frames_coded" in n}
-                if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
-                    raise RuntimeError(f"k_frame_rows / k_parse_frames_coded missing or using scratch: {ru}")
+                new = {n: u for n, u in ru.items()
+                       if "k_frame_rows" in n or "k_parse_frames_coded" in n or "k_parse_frame_headers" in n}
+                if len(new) != 3 or any(u.get("ScratchSize", 0) for u in new.values()):
+                    raise RuntimeError("k_frame_rows / k_parse_frames_coded / k_parse_frame_headers missing or "
+                                       f"using scratch: {ru}")
+                if verbose:
+                    for n, u in sorted(ru.items()):
+                        print(f"  {n}: {u}")
+            if s == "qf_relay.hip":
+                # k_combine_rows_at keeps in-flight load destinations in
+                # registers like the other k_combine_* kernels (DESIGN.md
+                # 3.12): a spill would copy them before the data lands
+                ru = _check_no_scratch(err)
+                new = {n: u for n, u in ru.items() if "k_combine_rows_at" in n}
+                if len(new) != 1 or any(u.get("ScratchSize", 0) for u in new.values()):
+                    raise RuntimeError(f"k_combine_rows_at missing or using scratch: {ru}")
                 if verbose:
                     for n, u in sorted(ru.items()):
                         print(f"  {n}: {u}")

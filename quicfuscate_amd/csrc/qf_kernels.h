@@ -167,9 +167,52 @@ struct RecodePrepareArgs {
     uint8_t* out_coeffs;         // [G][m][k]
     int32_t* status;
     uint32_t k, r, m, max_rows, passes, G;
+    // qf_recode_frames_dev (qf_relay.hip): row s of generation g is row_len
+    // bytes at row_off from the generation's source region (nullptr: the
+    // strided rows of qf_recode_batch, and none of the fields below is used).
+    // A row with row_len > L, row_off % 16 != 0 or row_off + row_len >
+    // src_gen_stride makes the generation QF_EINVAL.  coef_out then holds
+    // 48-byte pair records, (max_rows + 1) / 2 + 1 of them per generation and
+    // pass: pair t = {off[2t], off[2t+1], len[2t], len[2t+1]} (u32), then the
+    // coefficient records of slots 2t and 2t + 1.  Slots at and after n have
+    // a zero record, offset row_off[n - 1] (0 when n == 0) and length 0.
+    // min_len receives the shortest and out_len (nullable, [G][m]) the longest
+    // row_len of the n rows, both 0 when the status is not QF_OK.
+    const uint32_t* row_off = nullptr;   // [G][max_rows]
+    const uint32_t* row_len = nullptr;   // [G][max_rows]
+    uint32_t* min_len = nullptr;         // [G]
+    uint32_t* out_len = nullptr;
+    uint64_t src_gen_stride = 0;
+    uint32_t L = 0;
 };
 size_t recode_prepare_lds_bytes(uint32_t k, uint32_t m, uint32_t max_rows);
 hipError_t launch_recode_prepare(const RecodePrepareArgs& a, hipStream_t st);
+
+// Recode payload pass over rows read where they lie (qf_recode_frames_dev,
+// k_combine_rows_at in qf_relay.hip): one 16-output pass
+//   dst[g][j] = XOR_s coef[g][s][j] * row(g, s)   for j < n_out
+// with row(g, s) the len bytes at src + g*src_gen_stride + off, zero beyond
+// them.  coef: this pass's 48-byte pair records ({off, off, len, len} and two
+// coefficient records) and min_len as RecodePrepareArgs describes them.
+constexpr uint32_t kPairRecBytes = 48;
+struct CombineRowsAtArgs {
+    const uint8_t* src;
+    uint64_t src_gen_stride;
+    uint8_t* dst;
+    uint64_t dst_gen_stride;
+    uint64_t dst_row_stride;
+    const uint8_t* coef;
+    uint64_t coef_gen_stride;
+    const uint32_t* bound;
+    const uint32_t* min_len;
+    const uint32_t* tab256;
+    uint32_t n_out;      // output rows of this pass, 1..16
+    uint32_t L;
+    uint32_t Lu;
+    uint32_t max_rows;
+    uint64_t total_units;
+};
+hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st);
 
 // Innovative-row filter (qf_rank_batch, qf_decode_innovative_batch;
 // qf_rank.hip): one wave per generation walks the slots in arrival order and

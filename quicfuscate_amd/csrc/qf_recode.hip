@@ -21,6 +21,8 @@
 //                     products run over the compacted list of coded slots,
 //                     lanes over columns, with the slots' vectors and the mix
 //                     entries in log form in LDS (exp / log tables of d_explog).
+//                     For qf_recode_frames_dev (qf_relay.hip) it also checks
+//                     the rows' (offset, length) and writes their descriptors.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -83,6 +85,11 @@ __global__ void __launch_bounds__(64) k_recode_prepare(RecodePrepareArgs a) {
         const uint32_t idx = s < n ? ridx[s] : 0;
         const bool coded = s < n && idx >= k;
         if (coded && !a.row_coeffs && idx - k >= a.r) bad = true;
+        if (a.row_off && s < n) {
+            // a row given by (offset, length): whole 16-byte units inside the region
+            const uint32_t off = a.row_off[(uint64_t)g * mr + s], len = a.row_len[(uint64_t)g * mr + s];
+            if (len > a.L || (off & 15) || (uint64_t)off + len > a.src_gen_stride) bad = true;
+        }
         if (s < n && idx < k) next[s] = (uint16_t)atomicExch(&head[idx], s);   // 0xFFFFFFFF -> kNone16
         const uint64_t bc = __ballot(coded);
         if (coded) cslot[ncoded + __popcll(bc & lt_mask)] = (uint16_t)s;
@@ -90,7 +97,8 @@ __global__ void __launch_bounds__(64) k_recode_prepare(RecodePrepareArgs a) {
     }
     __syncthreads();
     if (__any(bad)) {
-        // a coded row without a coefficient vector: the generation's outputs are zero
+        // a coded row without a coefficient vector (or a row that is not inside
+        // its source region): the generation's outputs are zero
         status = QF_EINVAL;
         n = 0;
         ncoded = 0;
@@ -153,9 +161,12 @@ __global__ void __launch_bounds__(64) k_recode_prepare(RecodePrepareArgs a) {
 
     // Coefficient records of the payload pass: slot s of pass p holds
     // M[16p .. 16p + 15][s]; slots >= n and the record at max_rows are zero.
+    // (Rows by offset: the record of slot s sits in pair record s / 2, behind
+    // the pair's 16 descriptor bytes, and the last pair is all zero slots.)
+    const uint32_t nrec = a.row_off ? 2 * ((mr + 1) / 2 + 1) : mr + 1;
     for (uint32_t p = 0; p < a.passes; ++p) {
         uint8_t* out = a.coef_out + ((uint64_t)p * a.G + g) * a.coef_gen_stride;
-        for (uint32_t s = lane; s <= mr; s += 64) {
+        for (uint32_t s = lane; s < nrec; s += 64) {
             uint32_t w[4] = {0, 0, 0, 0};
             if (s < n) {
 #pragma unroll
@@ -165,8 +176,43 @@ __global__ void __launch_bounds__(64) k_recode_prepare(RecodePrepareArgs a) {
                     w[q >> 2] |= v << (8 * (q & 3));
                 }
             }
-            *reinterpret_cast<uint4*>(out + (uint64_t)s * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+            const uint64_t at = a.row_off ? (uint64_t)(s >> 1) * kPairRecBytes + 16 + (s & 1) * 16 : (uint64_t)s * 16;
+            *reinterpret_cast<uint4*>(out + at) = make_uint4(w[0], w[1], w[2], w[3]);
         }
+    }
+
+    // Row descriptors of the in-place payload pass (qf_relay.hip), in front of
+    // each pair's records: offset and length of slot s, the offset of slot
+    // n - 1 and length 0 at and after n, so a lane of k_combine_rows_at that
+    // runs past its generation's rows finds a readable unit and a zero record.
+    if (a.row_off) {
+        const uint32_t* ro = a.row_off + (uint64_t)g * mr;
+        const uint32_t* rl = a.row_len + (uint64_t)g * mr;
+        const uint32_t last_off = n ? ro[n - 1] : 0;
+        uint32_t mx = 0, mn = 0xFFFFFFFFu;
+        for (uint32_t s = lane; s < nrec; s += 64) {
+            uint32_t off = last_off, len = 0;
+            if (s < n) {
+                off = ro[s];
+                len = rl[s];
+                mx = max(mx, len);
+                mn = min(mn, len);
+            }
+            for (uint32_t p = 0; p < a.passes; ++p) {
+                uint32_t* pair = reinterpret_cast<uint32_t*>(a.coef_out + ((uint64_t)p * a.G + g) * a.coef_gen_stride +
+                                                             (uint64_t)(s >> 1) * kPairRecBytes);
+                pair[s & 1] = off;
+                pair[2 + (s & 1)] = len;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            mx = max(mx, (uint32_t)__shfl_xor(mx, o, 64));
+            mn = min(mn, (uint32_t)__shfl_xor(mn, o, 64));
+        }
+        if (lane == 0) a.min_len[g] = n ? mn : 0;
+        if (a.out_len)
+            for (uint32_t j = lane; j < m; j += 64) a.out_len[(uint64_t)g * m + j] = mx;
     }
 
     // Output vectors, lanes over columns: the systematic slots of column i
@@ -202,7 +248,11 @@ __global__ void __launch_bounds__(64) k_recode_prepare(RecodePrepareArgs a) {
 hipError_t launch_recode_prepare(const RecodePrepareArgs& a, hipStream_t st) {
     if (a.G == 0) return hipSuccess;
     if (a.k == 0 || a.k > 255 || a.m == 0 || a.m > 64 || a.max_rows == 0 || a.max_rows > 255 ||
-        a.k + a.r > 256 || a.passes != (a.m + 15) / 16 || a.coef_gen_stride < ((uint64_t)a.max_rows + 1) * 16)
+        a.k + a.r > 256 || a.passes != (a.m + 15) / 16)
+        return hipErrorInvalidValue;
+    const uint64_t rec_bytes = a.row_off ? ((uint64_t)(a.max_rows + 1) / 2 + 1) * kPairRecBytes
+                                         : ((uint64_t)a.max_rows + 1) * 16;
+    if (a.coef_gen_stride < rec_bytes || (a.coef_gen_stride & 15) || (a.row_off && (!a.row_len || !a.min_len)))
         return hipErrorInvalidValue;
     const size_t lds = recode_prepare_lds_bytes(a.k, a.m, a.max_rows);
     if (lds > 160 * 1024) return hipErrorInvalidValue;

@@ -1,0 +1,346 @@
+// qf_relay.hip -- a relay step that recodes straight from the received frame
+// slots: qf_parse_frame_headers_dev leaves every payload in
+// its slot and describes a row as (offset, length); qf_recode_frames_dev is
+// qf_recode_batch over rows given that way.
+//
+//  k_combine_rows_at  the recode's payload pass, k_combine_slots with the rows
+//                     read where they lie.  One lane per 16-byte unit of the
+//                     output rows, the same 16-byte coefficient records and
+//                     fma_rows_slots products, ceil(m / 16) passes.  Row s of
+//                     a lane's generation comes from the {offset, length}
+//                     that k_recode_prepare writes in front of the records
+//                     of each slot pair (one 48-byte pair record: two
+//                     offsets, two lengths, two coefficient records), so a
+//                     slot pair costs five loads from two addresses against
+//                     k_combine_slots' four from four, and the offsets of
+//                     pair t + 2 are in flight while pair t multiplies.
+//                     Full path (every lane of the wave has its whole unit
+//                     inside every row of its generation: 16u + 16 <= the
+//                     generation's shortest row): asm-pipelined loads as
+//                     k_combine_slots, no masks.  Ragged path: a unit is
+//                     loaded only when it holds a byte of the row and is
+//                     masked to its valid bytes.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+#include <string>
+
+#include "qf_fec.h"
+#include "qf_kernels.h"
+#include "qf_gf_dev.h"
+#include "qf_internal.h"
+
+namespace qf {
+
+namespace {
+
+// Asm loads of a 48-byte pair record: the two row offsets (its first 8 bytes)
+// and the two coefficient records (bytes 16 and 32).  The pair is the same for
+// every lane, so its address is a scalar base (the pass's records + the pair's
+// offset) plus the lane's 32-bit generation offset: no address arithmetic on
+// the vector unit and one register per lane for all of a generation's records.
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+QF_DEV void aload_offs(v2u& r, uint32_t gen_off, const uint8_t* pair) {
+    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(r) : "v"(gen_off), "s"(pair) : "memory");
+}
+QF_DEV void aload_rec_a(v4u& r, uint32_t gen_off, const uint8_t* pair) {
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:16" : "=v"(r) : "v"(gen_off), "s"(pair) : "memory");
+}
+QF_DEV void aload_rec_b(v4u& r, uint32_t gen_off, const uint8_t* pair) {
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:32" : "=v"(r) : "v"(gen_off), "s"(pair) : "memory");
+}
+
+// Counted waits of the full path's asm loads.  Issue order in the steady
+// state, step t: D(t+2) Ca(t+1) Cb(t+1) | wait D(t+1) | Ra(t+1) Rb(t+1) |
+// wait pair t | multiply pair t  (D row offsets, C records, R row units).
+// Loads return in order: behind D(t+1) sit the four loads of pair t and the
+// three just issued (7); behind Rb(t) sit D(t+2) and the four of pair t+1 (5).
+// The prologue issues D(0) D(1) Ca(0) Cb(0) and waits for D(0) (3).
+QF_DEV void wait_offs_first(v2u& d) { asm volatile("s_waitcnt vmcnt(3)" : "+v"(d)::"memory"); }
+QF_DEV void wait_offs(v2u& d) { asm volatile("s_waitcnt vmcnt(7)" : "+v"(d)::"memory"); }
+QF_DEV void wait_pair(v4u& a, v4u& b, v4u& c, v4u& d) {
+    asm volatile("s_waitcnt vmcnt(5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
+}
+QF_DEV void wait_all(v2u& o, v4u& a, v4u& b, v4u& c, v4u& d) {
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(o), "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
+}
+
+QF_DEV uint32_t low_bytes_mask(uint32_t nb) { return nb >= 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1; }
+
+// The unit at p of a row of len bytes, u16 = 16 * unit index: the bytes of the
+// unit at and after len are zero, and a unit without a valid byte is not loaded.
+QF_DEV uint4 load_row_unit(const uint8_t* p, uint32_t len, uint32_t u16) {
+    uint4 x = make_uint4(0, 0, 0, 0);
+    if (len > u16) {
+        x = *reinterpret_cast<const uint4*>(p);
+        const uint32_t v = len - u16;
+        if (v < 16) {
+            x.x &= low_bytes_mask(v);
+            x.y &= low_bytes_mask(v > 4 ? v - 4 : 0);
+            x.z &= low_bytes_mask(v > 8 ? v - 8 : 0);
+            x.w &= low_bytes_mask(v > 12 ? v - 12 : 0);
+        }
+    }
+    return x;
+}
+
+// One wave-item.  srcp: the lane's unit in its generation's source region at
+// offset 0 (region + 16u); gen_off: the generation's pair records from a.coef
+// (below 2^31, launch_combine_rows_at).  Pairs past the last one, (max_rows +
+// 1) / 2, which holds zero slots only, are clamped to it.
+template <int R, bool FULL>
+QF_DEV void rows_at_item(const CombineRowsAtArgs& a, const uint32_t* __restrict__ tab256, const uint8_t* srcp,
+                         uint8_t* outp, uint32_t gen_off, uint32_t u16, uint32_t nbytes, uint32_t e_lane,
+                         uint32_t smax) {
+    const uint32_t tz = (a.max_rows + 1) / 2;
+    uint4 acc[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j] = make_uint4(0, 0, 0, 0);
+    const uint32_t npairs = (smax + 1) / 2;
+#define QF_PAIR(t) (a.coef + (uint64_t)((t) < tz ? (t) : tz) * kPairRecBytes)
+    if (!FULL) {
+        for (uint32_t t = 0; t < npairs; ++t) {
+            const uint4* pr = reinterpret_cast<const uint4*>(QF_PAIR(t) + gen_off);
+            const uint4 d = pr[0];   // off, off, len, len
+            const uint4 xa = load_row_unit(srcp + (uint64_t)d.x, d.z, u16);
+            const uint4 xb = load_row_unit(srcp + (uint64_t)d.y, d.w, u16);
+            fma_rows_slots<R>(acc, tab256, xa, xb, pr[1], pr[2]);
+        }
+    } else {
+        v2u d[2];
+        v4u pa[2], pb[2], qa[2], qb[2];
+        aload_offs(d[0], gen_off, QF_PAIR(0u));
+        aload_offs(d[1], gen_off, QF_PAIR(1u));
+        aload_rec_a(qa[0], gen_off, QF_PAIR(0u));
+        aload_rec_b(qb[0], gen_off, QF_PAIR(0u));
+        wait_offs_first(d[0]);
+        aload16(pa[0], srcp + (uint64_t)d[0].x);
+        aload16(pb[0], srcp + (uint64_t)d[0].y);
+        for (uint32_t t = 0; t < npairs; t += 2) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const int n = c ^ 1;
+                const uint32_t tt = t + c;
+                aload_offs(d[c], gen_off, QF_PAIR(tt + 2));
+                aload_rec_a(qa[n], gen_off, QF_PAIR(tt + 1));
+                aload_rec_b(qb[n], gen_off, QF_PAIR(tt + 1));
+                wait_offs(d[n]);
+                aload16(pa[n], srcp + (uint64_t)d[n].x);
+                aload16(pb[n], srcp + (uint64_t)d[n].y);
+                wait_pair(qa[c], qb[c], pa[c], pb[c]);
+                fma_rows_slots<R>(acc, tab256, to_u4(pa[c]), to_u4(pb[c]), to_u4(qa[c]), to_u4(qb[c]));
+            }
+        }
+        wait_all(d[0], pa[0], pb[0], qa[0], qb[0]);
+        wait_all(d[1], pa[1], pb[1], qa[1], qb[1]);
+    }
+#undef QF_PAIR
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        if ((uint32_t)j < e_lane) {
+            if (FULL) store_unit(outp + (uint64_t)j * a.dst_row_stride, acc[j], 16);
+            else store_unit(outp + (uint64_t)j * a.dst_row_stride, acc[j], nbytes);
+        }
+    }
+}
+
+template <int R>
+QF_DEV void rows_at_dispatch(const CombineRowsAtArgs& a, const uint32_t* tab256, const uint8_t* srcp, uint8_t* outp,
+                             uint32_t gen_off, uint32_t u16, uint32_t nbytes, uint32_t e_lane, uint32_t smax,
+                             bool full) {
+    if (full) rows_at_item<R, true>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax);
+    else rows_at_item<R, false>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax);
+}
+
+__global__ void __launch_bounds__(256, 3) k_combine_rows_at(CombineRowsAtArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tab256[256 * 8];
+    {
+        const uint4* g = reinterpret_cast<const uint4*>(a.tab256);
+        uint4* l = reinterpret_cast<uint4*>(tab256);
+        for (uint32_t w = threadIdx.x; w < 512; w += blockDim.x) l[w] = g[w];
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wpb = blockDim.x >> 6;
+    const uint32_t wave = blockIdx.x * wpb + (threadIdx.x >> 6);
+    const uint32_t nwaves = gridDim.x * wpb;
+    for (uint64_t base = (uint64_t)wave * 64; base < a.total_units; base += (uint64_t)nwaves * 64) {
+        // a lane past the last unit shadows the wave's first lane and stores nothing
+        const bool active = base + lane < a.total_units;
+        const uint64_t f = active ? base + lane : base;
+        const uint64_t g = f / a.Lu;
+        const uint32_t u = (uint32_t)(f - g * a.Lu);
+        const uint32_t u16 = u * 16;
+        const uint8_t* srcp = a.src + g * a.src_gen_stride + u16;
+        uint8_t* outp = a.dst + g * a.dst_gen_stride + u16;
+        const uint32_t gen_off = (uint32_t)(g * a.coef_gen_stride);
+        const uint32_t rem = a.L - u16;
+        const uint32_t nbytes = rem < 16 ? rem : 16;
+        const uint32_t e_lane = active ? a.n_out : 0;
+        const uint32_t smax = wave_max_u32(a.bound[g]);
+        const bool full = __all(u16 + 16 <= a.min_len[g]);
+        // smax == 0: every generation of the wave is not QF_OK; the ragged
+        // path then stores the zero rows without a load
+        if (a.n_out <= 4) rows_at_dispatch<4>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else if (a.n_out <= 8) rows_at_dispatch<8>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else if (a.n_out <= 12) rows_at_dispatch<12>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else rows_at_dispatch<16>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st) {
+    if (a.total_units == 0) return hipSuccess;
+    if (a.n_out == 0 || a.n_out > 16 || a.max_rows == 0 || a.Lu == 0 || a.Lu != (a.L + 15) / 16 || (a.src_gen_stride & 15) || (a.coef_gen_stride & 15) ||
+        a.coef_gen_stride < ((uint64_t)(a.max_rows + 1) / 2 + 1) * kPairRecBytes)
+        return hipErrorInvalidValue;
+    int occ = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_combine_rows_at, 256, 0);
+    if (e != hipSuccess) return e;
+    if (occ < 1) occ = 1;
+    const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 1) * occ;
+    // a lane addresses its generation's records by a 32-bit offset from
+    // a.coef: batches whose records exceed 2 GiB go in several launches
+    const uint64_t G = a.total_units / a.Lu;
+    const uint64_t g_max = 0x7FFFFFFFull / a.coef_gen_stride;
+    for (uint64_t g0 = 0; g0 < G; g0 += g_max) {
+        const uint64_t gn = G - g0 < g_max ? G - g0 : g_max;
+        CombineRowsAtArgs c = a;
+        c.src += g0 * a.src_gen_stride;
+        c.dst += g0 * a.dst_gen_stride;
+        c.coef += g0 * a.coef_gen_stride;
+        c.bound += g0;
+        c.min_len += g0;
+        c.total_units = gn * a.Lu;
+        const uint64_t waves = (c.total_units + 63) / 64;
+        uint64_t blocks = (waves + 3) / 4;
+        if (blocks > cap) blocks = cap;
+        hipLaunchKernelGGL(k_combine_rows_at, dim3((uint32_t)blocks), dim3(256), 0, st, c);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_parse_frame_headers(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
+                                      const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
+                                      uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint16_t* row_index,
+                                      uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len, uint32_t* row_off,
+                                      int32_t* frame_status, hipStream_t st);   // qf_wire.hip
+
+}  // namespace qf
+
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+extern "C" int qf_parse_frame_headers_dev(qf_ctx* ctx, uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows,
+                                          const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
+                                          const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
+                                          uint16_t* row_index, uint32_t* n_rows, uint8_t* row_coeffs,
+                                          uint32_t* row_len, uint32_t* row_off, int32_t* frame_status) {
+    if (!ctx) return QF_EINVAL;
+    if (k == 0 || k > 256) return QF_EINVAL;
+    if (G == 0) return QF_OK;
+    if (max_rows == 0 || max_rows > 1024 || L == 0) return QF_EINVAL;
+    if (!frames || !frame_len || !ids || !row_index || !n_rows || !row_coeffs || !row_len || !row_off || !frame_status)
+        return QF_EINVAL;
+    if ((frame_stride & 15) || !aligned16(frames)) return QF_EINVAL;
+    // row_off is a u32 offset into a generation's max_rows * frame_stride bytes
+    if (frame_stride > (1ull << 32) / max_rows) return QF_EINVAL;
+    std::unique_lock<std::mutex> lk;
+    int s = qf::ctx_lock(ctx, lk);
+    if (s) return s;
+    hipStream_t st = qf::ctx_stream(ctx);
+    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
+    QF_CHECK_HIP(qf::launch_parse_frame_headers(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
+                                                max_rows, row_index, n_rows, row_coeffs, row_len, row_off,
+                                                frame_status, st));
+    qf::ctx_prof_end(ctx, st, ev, "k_parse_frame_headers");
+    return QF_OK;
+}
+
+extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint32_t G, const uint8_t* src,
+                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
+                                    const uint32_t* n_rows, const uint8_t* row_coeffs, const uint8_t* mix,
+                                    uint64_t seed, uint8_t* out, uint8_t* out_coeffs, uint32_t* out_len,
+                                    int32_t* status) {
+    if (!ctx || !sh) return QF_EINVAL;
+    const uint32_t k = sh->k, L = sh->L, max_rows = sh->max_rows, m = sh->m;
+    if (k == 0 || k > 255 || max_rows == 0 || max_rows > 255 || m == 0 || m > 64 || L == 0 || sh->flags != 0 ||
+        sh->reserved != 0)
+        return QF_EINVAL;
+    if (sh->out_row_stride < L) return QF_EINVAL;
+    if (G == 0) return QF_OK;
+    if (!src || !row_off || !row_len || !row_index || !row_coeffs || !out || !out_coeffs || !status) return QF_EINVAL;
+    if (!aligned16(src) || (sh->src_gen_stride & 15) || !aligned16(out) || (sh->out_row_stride & 15) ||
+        (sh->out_gen_stride & 15))
+        return QF_EINVAL;
+    std::unique_lock<std::mutex> lk;
+    int s = qf::ctx_lock(ctx, lk);
+    if (s) return s;
+    hipStream_t st = qf::ctx_stream(ctx);
+    // workspace: pair records [pass][G][((max_rows + 1) / 2 + 1) * 48] | n_out[G] | bound[G] | min_len[G]
+    const uint32_t passes = (m + 15) / 16;
+    const uint64_t coef_gen_stride = ((uint64_t)(max_rows + 1) / 2 + 1) * qf::kPairRecBytes;
+    const size_t off_nout = round_up((size_t)passes * G * coef_gen_stride, 256);
+    const size_t off_bound = off_nout + round_up((size_t)G * 4, 256);
+    const size_t off_minlen = off_bound + round_up((size_t)G * 4, 256);
+    uint8_t* w = nullptr;
+    s = qf::ctx_work(ctx, off_minlen + (size_t)G * 4, &w);
+    if (s) return s;
+    uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
+    uint32_t* d_minlen = reinterpret_cast<uint32_t*>(w + off_minlen);
+    qf::RecodePrepareArgs pa{};
+    pa.row_index = row_index;
+    pa.n_rows = n_rows;
+    pa.row_coeffs = row_coeffs;
+    pa.mix = mix;
+    pa.explog = qf::ctx_explog(ctx);
+    pa.seed = seed;
+    pa.coef_out = w;
+    pa.coef_gen_stride = coef_gen_stride;
+    pa.n_out = reinterpret_cast<uint32_t*>(w + off_nout);
+    pa.bound = d_bound;
+    pa.out_coeffs = out_coeffs;
+    pa.status = status;
+    pa.k = k;
+    pa.r = 0;
+    pa.m = m;
+    pa.max_rows = max_rows;
+    pa.passes = passes;
+    pa.G = G;
+    pa.row_off = row_off;
+    pa.row_len = row_len;
+    pa.min_len = d_minlen;
+    pa.out_len = out_len;
+    pa.src_gen_stride = sh->src_gen_stride;
+    pa.L = L;
+    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
+    QF_CHECK_HIP(qf::launch_recode_prepare(pa, st));
+    qf::ctx_prof_end(ctx, st, ev, "k_recode_prepare");
+    const uint32_t Lu = (L + 15) / 16;
+    for (uint32_t p = 0; p < passes; ++p) {
+        qf::CombineRowsAtArgs a{};
+        a.src = src;
+        a.src_gen_stride = sh->src_gen_stride;
+        a.dst = out + (uint64_t)p * 16 * sh->out_row_stride;
+        a.dst_gen_stride = sh->out_gen_stride;
+        a.dst_row_stride = sh->out_row_stride;
+        a.coef = w + (uint64_t)p * G * coef_gen_stride;
+        a.coef_gen_stride = coef_gen_stride;
+        a.bound = d_bound;
+        a.min_len = d_minlen;
+        a.tab256 = qf::ctx_tab256(ctx);
+        a.n_out = m - p * 16 < 16 ? m - p * 16 : 16;
+        a.L = L;
+        a.Lu = Lu;
+        a.max_rows = max_rows;
+        a.total_units = (uint64_t)G * Lu;
+        ev = qf::ctx_prof_begin(ctx, st);
+        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st));
+        qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");
+    }
+    return QF_OK;
+}

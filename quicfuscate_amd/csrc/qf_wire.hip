@@ -8,6 +8,8 @@
 //                         slots (any coefficient vector)
 //   k_parse_frames_coded  frames at an offset in their slots -> rows / row_index /
 //                         n_rows / row_coeffs / row_len, any coefficient vector
+//   k_parse_frame_headers the same decisions from the headers alone: row_off /
+//                         row_len instead of copied rows
 //
 // Payloads sit at byte offset 1 or 3 + k inside a frame, so the copy loops
 // move 16-byte blocks assembled from aligned dwords with v_alignbit (one
@@ -463,9 +465,167 @@ __global__ void __launch_bounds__(256) k_parse_frames_coded(ParseCodedArgs a) {
     }
 }
 
+struct ParseHeadersArgs {
+    const uint8_t* frames;
+    uint64_t frame_stride;
+    const uint32_t* frame_len;
+    const uint32_t* frame_off;  // NULL: 0
+    const uint64_t* ids;
+    const uint32_t* n_frames;
+    uint16_t* row_index;
+    uint32_t* n_rows;
+    uint8_t* row_coeffs;
+    uint32_t* row_len;
+    uint32_t* row_off;
+    int32_t* frame_status;
+    uint32_t k, L, max_rows;
+};
+
+// one 256-thread block per generation; the decisions of k_parse_frames_coded,
+// the payloads left where they are: an accepted row is (row_off, row_len) into
+// the generation's frame region, and must start at a multiple of 16 in its
+// slot.  Reads the 3 header bytes and the k vector bytes of a frame only.
+__global__ void __launch_bounds__(256) k_parse_frame_headers(ParseHeadersArgs a) {
+    __shared__ uint32_t slot_of[1024];   // frame -> output slot (or ~0)
+    __shared__ uint32_t pay_of[1024];    // payload start, from the slot's first byte
+    __shared__ uint16_t idx_of[1024];    // column of a systematic frame, k for a coded one
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t g = blockIdx.x;
+    const uint32_t nf = a.n_frames ? min(a.n_frames[g], a.max_rows) : a.max_rows;
+    uint32_t base = 0;
+    for (uint32_t s0 = 0; s0 < nf; s0 += blockDim.x) {
+        const uint32_t s = s0 + threadIdx.x;
+        int32_t st = QF_OK;
+        uint32_t idx = 0xFFFF, pay = 0, plen = 0;
+        if (s < nf) {
+            const uint64_t fi = (uint64_t)g * a.max_rows + s;
+            const uint32_t flen = a.frame_len[fi];
+            const uint32_t foff = a.frame_off ? a.frame_off[fi] : 0;
+            const uint8_t* fr = a.frames + fi * a.frame_stride + foff;
+            uint32_t off = 0;
+            if (flen == 0 || (uint64_t)foff + flen > a.frame_stride) {
+                st = QF_EINVAL;  // "Raw data is empty", or not inside its slot
+            } else if (fr[0] == 1) {
+                off = 1;
+                idx = (uint32_t)(a.ids[fi] % a.k);  // decoder.rs:684
+            } else if (flen < 3) {
+                st = QF_ETOOSMALL;  // coefficient length missing (encoder.rs:33-38)
+            } else {
+                const uint32_t cl = ((uint32_t)fr[1] << 8) | fr[2];
+                if (flen < 3 + cl) st = QF_ETOOSMALL;  // coefficients truncated
+                else if (cl != a.k) st = QF_ERANGE;
+                off = 3 + cl;
+                idx = a.k;
+            }
+            if (st == QF_OK) {
+                plen = flen - off;
+                pay = foff + off;
+                // a payload that cannot be read in place: longer than L, or not
+                // at a multiple of 16 in its slot
+                if (plen > a.L || (pay & 15)) st = QF_EINVAL;
+            }
+            a.frame_status[fi] = st;
+        }
+        const bool ok = s < nf && st == QF_OK;
+        // block-wide exclusive prefix of ok (4 waves)
+        const uint64_t bal = __ballot(ok);
+        const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+        const uint32_t before = __popcll(bal & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
+        if (lane == 0) wave_cnt[w] = __popcll(bal);
+        __syncthreads();
+        uint32_t woff = 0;
+        for (uint32_t q = 0; q < w; ++q) woff += wave_cnt[q];
+        uint32_t total = 0;
+        for (uint32_t q = 0; q < 4; ++q) total += wave_cnt[q];
+        if (s < nf) {   // nf <= max_rows <= 1024
+            slot_of[s] = ok ? base + woff + before : 0xFFFFFFFFu;
+            pay_of[s] = pay;
+            idx_of[s] = (uint16_t)idx;
+        }
+        if (ok) {
+            const uint64_t o = (uint64_t)g * a.max_rows + base + woff + before;
+            a.row_index[o] = (uint16_t)idx;
+            a.row_len[o] = plen;
+            a.row_off[o] = (uint32_t)(s * a.frame_stride) + pay;   // max_rows * frame_stride <= 2^32
+        }
+        base += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.n_rows[g] = base;
+    __syncthreads();
+    // 16-byte blocks of every accepted row's coefficient vector (the unit
+    // vector of a systematic frame)
+    const uint32_t cpr = (a.k + 15) / 16;
+    const uint32_t nwork = nf * cpr;
+    for (uint32_t w = threadIdx.x; w < nwork; w += blockDim.x) {
+        const uint32_t s = w / cpr, u = w - s * cpr;
+        const uint32_t slot = slot_of[s];
+        if (slot == 0xFFFFFFFFu) continue;
+        const uint64_t fi = (uint64_t)g * a.max_rows + s;
+        const uint8_t* fslot = a.frames + fi * a.frame_stride;
+        const uint32_t pay = pay_of[s];
+        const uint32_t c0 = u * 16;
+        const uint32_t cend = min(c0 + 16, a.k);
+        uint8_t* cd = a.row_coeffs + ((uint64_t)g * a.max_rows + slot) * a.k;
+        const uint32_t idx = idx_of[s];
+        const bool wide = c0 + 16 <= a.k && ((uintptr_t)(cd + c0) & 15) == 0;
+        if (idx < a.k) {
+            if (wide) {
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (idx >= c0 && idx < c0 + 16) {
+                    const uint32_t bit = 1u << (8 * (idx & 3));
+                    const uint32_t q = (idx - c0) >> 2;
+                    v.x = q == 0 ? bit : 0;
+                    v.y = q == 1 ? bit : 0;
+                    v.z = q == 2 ? bit : 0;
+                    v.w = q == 3 ? bit : 0;
+                }
+                *reinterpret_cast<uint4*>(cd + c0) = v;
+            } else {
+                for (uint32_t t = c0; t < cend; ++t) cd[t] = t == idx ? 1 : 0;
+            }
+            continue;
+        }
+        // the vector sits in front of the payload: bytes [pay - k, pay) of the
+        // slot; the readable bytes end with it (no payload byte is touched)
+        const uint32_t v0 = pay - a.k;
+        if (wide && can_copy16(v0 + c0, pay)) {
+            *reinterpret_cast<uint4*>(cd + c0) = load16(fslot, v0 + c0);
+        } else {
+            for (uint32_t t = c0; t < cend; ++t) cd[t] = fslot[v0 + t];
+        }
+    }
+}
+
 }  // namespace
 
 namespace qf {
+
+hipError_t launch_parse_frame_headers(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
+                                      const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
+                                      uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint16_t* row_index,
+                                      uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len, uint32_t* row_off,
+                                      int32_t* frame_status, hipStream_t st) {
+    ParseHeadersArgs a{};
+    a.frames = frames;
+    a.frame_stride = frame_stride;
+    a.frame_len = frame_len;
+    a.frame_off = frame_off;
+    a.ids = ids;
+    a.n_frames = n_frames;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.row_coeffs = row_coeffs;
+    a.row_len = row_len;
+    a.row_off = row_off;
+    a.frame_status = frame_status;
+    a.k = k;
+    a.L = L;
+    a.max_rows = max_rows;
+    if (G == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_parse_frame_headers, dim3(G), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_frame_rows(const uint8_t* rows, const uint16_t* row_index, const uint32_t* n_rows,
                              const uint8_t* row_coeffs, const uint32_t* row_len, const qf_frame_rows_shape& sh,

@@ -36,7 +36,7 @@ __all__ = [
     "QfError", "Context", "default_context", "init_gf_tables", "gf_mul", "gf_mul_table",
     "gf_mul_add", "gf_inv", "gf_mul_slice", "cauchy_coefficients", "MemoryPool", "Packet",
     "Encoder", "Decoder", "encode_batch", "decode_batch", "recode_batch", "Recoder",
-    "frame_payload_offset", "frame_rows", "parse_frames_coded",
+    "frame_payload_offset", "frame_rows", "parse_frames_coded", "parse_frame_headers", "recode_frames",
     "gf16_mul", "gf16_inv", "cauchy16_coefficients", "encode16_batch", "decode16_batch", "Encoder16", "Decoder16",
 ]
 
@@ -542,6 +542,70 @@ def parse_frames_coded(frames, frame_len, ids, rows, row_index, n_rows, frame_st
         _ptr(n_frames) if n_frames is not None else None,
         _ptr(rows), row_stride, rows_gen_stride, _ptr(row_index), _ptr(n_rows), _ptr(row_coeffs),
         _ptr(row_len) if row_len is not None else None, _ptr(frame_status)), "parse_frames_coded")
+
+
+def parse_frame_headers(frames, frame_len, ids, row_index, n_rows, frame_status, row_coeffs, row_len, row_off,
+                        k: int, Lb: int, *, max_rows: int, frame_stride: int, G: int, n_frames=None,
+                        frame_off=None, ctx: Optional[Context] = None) -> None:
+    """qf_parse_frame_headers_dev: parse_frames_coded that reads the headers
+    only.  The payloads stay in their slots; compacted row c of generation g is
+    the row_len[g, c] bytes at byte row_off[g, c] of the generation's frame
+    region (frames + g*max_rows*frame_stride), the input of recode_frames.  A
+    frame whose payload does not start at a multiple of 16 in its slot is
+    QF_EINVAL."""
+    _need(frames, G * max_rows * frame_stride, "frames")
+    _need(frame_len, 4 * G * max_rows, "frame_len")
+    _need(ids, 8 * G * max_rows, "ids")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(n_rows, 4 * G, "n_rows")
+    _need(frame_status, 4 * G * max_rows, "frame_status")
+    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need(row_len, 4 * G * max_rows, "row_len")
+    _need(row_off, 4 * G * max_rows, "row_off")
+    if n_frames is not None:
+        _need(n_frames, 4 * G, "n_frames")
+    if frame_off is not None:
+        _need(frame_off, 4 * G * max_rows, "frame_off")
+    ctx = ctx or default_context()
+    check(L._lib().qf_parse_frame_headers_dev(
+        ctx.handle, k, Lb, G, max_rows, _ptr(frames), frame_stride, _ptr(frame_len),
+        _ptr(frame_off) if frame_off is not None else None, _ptr(ids),
+        _ptr(n_frames) if n_frames is not None else None,
+        _ptr(row_index), _ptr(n_rows), _ptr(row_coeffs), _ptr(row_len), _ptr(row_off), _ptr(frame_status)),
+        "parse_frame_headers")
+
+
+def recode_frames(src, row_off, row_len, row_index, row_coeffs, out, out_coeffs, status, k: int, m: int, Lb: int, *,
+                  max_rows: int, src_gen_stride: int, out_row_stride: int, out_gen_stride: int, G: int,
+                  n_rows=None, mix=None, seed: int = 0, out_len=None, ctx: Optional[Context] = None) -> None:
+    """qf_recode_frames_dev: recode_batch (r = 0) over rows that lie where they
+    were received: row c of generation g is the row_len[g, c] bytes at
+    src + g*src_gen_stride + row_off[g, c], zero padded to Lb (what
+    parse_frame_headers leaves, with src = the frames and src_gen_stride =
+    max_rows * frame_stride).  out_len: optional [G, m] u32, the longest row
+    length of each generation (frame_rows' row_len for the recoded rows)."""
+    _need(src, G * src_gen_stride, "src")
+    _need(row_off, 4 * G * max_rows, "row_off")
+    _need(row_len, 4 * G * max_rows, "row_len")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need(out, _span(G, out_gen_stride, m, out_row_stride, Lb), "out")
+    _need(out_coeffs, G * m * k, "out_coeffs (m vectors of k bytes per generation)")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if mix is not None:
+        _need(mix, G * m * max_rows, "mix")
+    if out_len is not None:
+        _need(out_len, 4 * G * m, "out_len")
+    ctx = ctx or default_context()
+    sh = L.RecodeFramesShape(k, Lb, max_rows, m, 0, 0, src_gen_stride, out_row_stride, out_gen_stride)
+    check(L._lib().qf_recode_frames_dev(
+        ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
+        _ptr(mix) if mix is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _ptr(out), _ptr(out_coeffs), _ptr(out_len) if out_len is not None else None, _ptr(status)),
+        "recode_frames")
 
 
 # ---------------------------------------------------------------------------
