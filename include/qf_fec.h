@@ -508,6 +508,76 @@ int qf_decode_innovative_batch(qf_ctx *ctx, const qf_decode_shape *shape, uint32
                                int32_t *status_dev, uint32_t *rank_dev, uint8_t *innovative_dev);
 
 /* ---------------------------------------------------------------------------
+ * The same decode from rows that lie where they were received (receiver, in
+ * place).  No reference counterpart.  qf_decode_innovative_batch over rows
+ * given as in qf_recode_frames_dev:
+ *   rows[g][c] = the row_len_dev[g*max_rows + c] bytes at
+ *                src_dev + g*src_gen_stride + row_off_dev[g*max_rows + c],
+ *                zero padded to L
+ * which is what qf_parse_frame_headers_dev leaves (src_dev = frames_dev,
+ * src_gen_stride = max_rows * frame_stride).  rec_dev, rec_index_dev,
+ * n_rec_dev, status_dev, rank_dev (nullable) and innovative_dev (nullable) are
+ * byte for byte what qf_decode_innovative_batch writes for those rows with the
+ * same k, r, max_rows, row_index_dev, n_rows_dev (NULL: max_rows) and
+ * row_coeffs_dev (required here, as in qf_recode_frames_dev).
+ * Writes: exactly L bytes per recovered row; rows n_rec[g] and above of a
+ * generation, and all rows of a generation that is not QF_OK, are not written
+ * (the device decode's rule; the recoder writes zeros instead).
+ * Further QF_EINVAL cases of status_dev[g]: one of the generation's n rows has
+ * row_len > L, row_off % 16 != 0 or row_off + row_len > src_gen_stride.  Such
+ * a generation has n_rec 0 and no byte of rec_dev written; rank_dev and
+ * innovative_dev still hold what qf_rank_batch writes (they depend on the
+ * vectors only).  row_len == 0 is legal.
+ * src_slot_dev (nullable), one u16 per source at g*k + i: for a QF_OK
+ * generation the slot c of the accepted systematic row of source i (the packet
+ * is the row_len_dev[g*max_rows + c] bytes at row_off_dev[g*max_rows + c]), or
+ * 0xFFFF when source i was recovered (the packet is then row m of rec_dev with
+ * rec_index_dev[m] == i); all k entries 0xFFFF for a generation that is not
+ * QF_OK.  With it the k packets of a generation are found without a host scan.
+ * Reads: only aligned 16-byte units of an accepted (innovative) row that hold
+ * at least one of its bytes; the payload of a non-innovative slot is never
+ * read (qf_decode_innovative_batch reads it and multiplies it by zero).
+ * src_dev is never written and must not overlap rec_dev.
+ * Returns QF_EINVAL for k outside 1..256, max_rows outside 1..1024, min(k, r) >
+ * 128, L == 0, flags or reserved != 0, rec_row_stride < L, a NULL required
+ * pointer (src_dev, row_off_dev, row_len_dev, row_index_dev, row_coeffs_dev,
+ * n_rec_dev, status_dev, and rec_dev / rec_index_dev when min(k, r) > 0),
+ * src_dev, rec_dev or a stride not 16-byte aligned, or a shape whose control
+ * kernel would need more than 160 KB of LDS.  G == 0 is QF_OK.  The call
+ * clears qf_ctx_set_payload_stream / qf_ctx_set_payload_wait, as
+ * qf_decode_innovative_batch does.
+ * The payload runs ceil(min(k, r) / 16) passes of k_combine_rows_at, whatever
+ * the row length (the generated bit-sliced payload kernels are not used); a
+ * pass in which no generation has a row to write costs a launch and no row
+ * read.  Which sequence: for rows under 2,017 bytes use this one (with
+ * qf_parse_frame_headers_dev 0.66 of the copy sequence's time at k = 64, L =
+ * 1,200, 13 recovered rows; 0.92 with 64 recovered).  From 2,017 bytes on,
+ * qf_decode_innovative_batch runs the bit-sliced payload kernel and
+ * qf_parse_frames_coded_dev + qf_decode_innovative_batch is the faster
+ * sequence (this one takes 1.14 of its time at (196, 59), L = 9,000;
+ * DESIGN.md 3.13).
+ * ------------------------------------------------------------------------- */
+typedef struct qf_decode_frames_shape {
+    uint32_t k;              /* generation size, 1..256 */
+    uint32_t r;              /* bounds the recovered rows: up to min(k, r) <= 128 per generation */
+    uint32_t L;              /* payload bytes per recovered row, >= every row_len, >= 1 */
+    uint32_t max_rows;       /* input slots per generation, 1..1024 */
+    uint32_t flags;          /* 0 */
+    uint32_t reserved;       /* 0 */
+    uint64_t src_gen_stride; /* bytes of one generation's source region, % 16 == 0 */
+    uint64_t rec_row_stride;
+    uint64_t rec_gen_stride;
+} qf_decode_frames_shape;
+
+int qf_decode_frames_dev(qf_ctx *ctx, const qf_decode_frames_shape *shape, uint32_t G,
+                         const uint8_t *src_dev, const uint32_t *row_off_dev,
+                         const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                         const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                         uint8_t *rec_dev, uint16_t *rec_index_dev, uint32_t *n_rec_dev,
+                         int32_t *status_dev, uint32_t *rank_dev, uint8_t *innovative_dev,
+                         uint16_t *src_slot_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations
@@ -848,6 +918,10 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
  *   qf_frame_rows_dev           QF_FRAME_IN_PLACE, row_len_dev = out_len_dev
  * Receiver:
  *   qf_parse_frames_coded_dev   then qf_decode_innovative_batch on its outputs
+ * The same without the copy of the payloads out of their slots (the faster
+ * receiver sequence for rows under 2,017 bytes; the one above from there on):
+ *   qf_parse_frame_headers_dev  then qf_decode_frames_dev with src_dev = frames_in,
+ *                               src_gen_stride = max_rows * frame_stride
  * The intermediate rows belong to the caller.
  * ------------------------------------------------------------------------- */
 /* No reference counterpart (a layout rule): P = round_up(3 + k, 16) for k in

@@ -78,6 +78,14 @@ class RecodeFramesShape(ctypes.Structure):
     ]
 
 
+class DecodeFramesShape(ctypes.Structure):
+    """qf_decode_frames_shape (innovative decode from rows given as offset and length)."""
+    _fields_ = [
+        ("k", _U32), ("r", _U32), ("L", _U32), ("max_rows", _U32), ("flags", _U32), ("reserved", _U32),
+        ("src_gen_stride", _U64), ("rec_row_stride", _U64), ("rec_gen_stride", _U64),
+    ]
+
+
 class RankShape(ctypes.Structure):
     """qf_rank_shape (innovative-row filter)."""
     _fields_ = [("k", _U32), ("r", _U32), ("max_rows", _U32), ("flags", _U32)]
@@ -208,6 +216,8 @@ _SIGS = {
     "qf_parse_frame_headers_dev": (_I, [_P, _U32, _U32, _U32, _U32, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                         _P]),
     "qf_recode_frames_dev": (_I, [_P, ctypes.POINTER(RecodeFramesShape), _U32, _P, _P, _P, _P, _P, _P, _P, _U64,
+                                  _P, _P, _P, _P]),
+    "qf_decode_frames_dev": (_I, [_P, ctypes.POINTER(DecodeFramesShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   _P, _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),

@@ -907,6 +907,11 @@ int ctx_lock(qf_ctx* ctx, std::unique_lock<std::mutex>& lk) {
 }
 hipStream_t ctx_stream(qf_ctx* ctx) { return ctx->stream; }
 int ctx_num_cus(qf_ctx* ctx) { return ctx->num_cus; }
+void ctx_clear_payload_split(qf_ctx* ctx) {
+    std::lock_guard<std::mutex> g(ctx->mu);
+    ctx->has_payload_stream = ctx->payload_on_stream = false;
+    ctx->payload_wait = nullptr;
+}
 bool small_encode_enabled(qf_ctx* ctx) { return ctx->opt[QF_OPT_ENCODE_SMALL] != 0; }
 int64_t ctx_opt(qf_ctx* ctx, int opt) { return (opt >= 0 && opt < QF_OPT_COUNT) ? ctx->opt[opt] : 0; }
 int encode_ring_window(qf_ctx* ctx, uint32_t k, uint32_t first, uint32_t count, uint32_t L, const uint8_t* ring,

@@ -77,6 +77,26 @@ struct PrepareArgs {
     // qf_decode_innovative_batch: [G][max_rows] accept flags of k_rank_filter;
     // a slot is a candidate only if its byte is set (nullptr: every slot)
     const uint8_t* accept = nullptr;
+    // qf_decode_frames_dev (qf_relay.hip): row s of generation g is row_len
+    // bytes at row_off from the generation's source region (nullptr: strided
+    // rows, and none of the fields below is used).  A row among the n slots
+    // with row_len > L, row_off % 16 != 0 or row_off + row_len >
+    // src_gen_stride makes the generation QF_EINVAL.  coef_out then holds the
+    // 48-byte pair records of RecodePrepareArgs, compacted to the accepted
+    // slots in arrival order, (min(k, max_rows) + 1) / 2 + 1 of them per
+    // generation and pass: rows at and after the accepted count have a zero
+    // record, length 0 and the offset of the last accepted row (0 when none),
+    // and a generation that is not QF_OK or has nothing to recover counts as
+    // having accepted none.  bound receives the accepted count and min_len the
+    // shortest row_len among the accepted rows (both 0 for such a generation).
+    // src_slot (nullable, [G][k]): the accepted slot of each source's
+    // systematic row, 0xFFFF for an erased source or a generation not QF_OK.
+    const uint32_t* row_off = nullptr;   // [G][max_rows]
+    const uint32_t* row_len = nullptr;   // [G][max_rows]
+    uint32_t* min_len = nullptr;         // [G]
+    uint16_t* src_slot = nullptr;
+    uint64_t src_gen_stride = 0;
+    uint32_t L = 0;
 };
 
 // Decode control for the reference's Cauchy code (no row_coeffs): row
@@ -211,6 +231,11 @@ struct CombineRowsAtArgs {
     uint32_t Lu;
     uint32_t max_rows;
     uint64_t total_units;
+    // qf_decode_frames_dev: generation g writes clamp(n_out_gen[g] - 16 * pass,
+    // 0, 16) rows in this pass, and a generation without a row in it is not
+    // read (nullptr: n_out rows for every generation, the recoder's pass)
+    const uint32_t* n_out_gen = nullptr;
+    uint32_t pass = 0;
 };
 hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st);
 

@@ -474,6 +474,9 @@ QF_DEV uint8_t gmul(const PrepLds& L, uint32_t a, uint32_t b) {
     return L.exp[(uint32_t)L.log[a] + (uint32_t)L.log[b]];
 }
 
+// AT (qf_decode_frames_dev): the rows are given by offset and length
+// (PrepareArgs::row_off) and the records are the in-place payload pass's.
+template <bool AT>
 __global__ void __launch_bounds__(64) k_decode_prepare(PrepareArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t g = blockIdx.x;
@@ -510,6 +513,12 @@ __global__ void __launch_bounds__(64) k_decode_prepare(PrepareArgs a) {
         if (idx < k) {
             if (!acpt || acpt[s]) atomicMin(&L.first[idx], s);
         } else if (idx - k >= a.rep_limit) bad = true;
+        if (AT) {
+            // a row given by (offset, length): whole 16-byte units inside the
+            // region, whether the slot is accepted or not (k_recode_prepare's rule)
+            const uint32_t off = a.row_off[(uint64_t)g * a.max_rows + s], len = a.row_len[(uint64_t)g * a.max_rows + s];
+            if (len > a.L || (off & 15) || (uint64_t)off + len > a.src_gen_stride) bad = true;
+        }
     }
     for (uint32_t s = lane; s < a.max_rows; s += 64) L.slot_col[s] = 0xFFFF;
     __syncthreads();
@@ -638,11 +647,68 @@ __global__ void __launch_bounds__(64) k_decode_prepare(PrepareArgs a) {
     // Outputs.  Record layout per (pass, generation): max_rows slot records
     // of 16 coefficient bytes, then one all-zero record (slot max_rows) that
     // the payload pass reads for slots past a lane's bound.
-    if (lane < a.passes) {
+    if (!AT && lane < a.passes) {
         uint8_t* out = a.coef_out + ((uint64_t)lane * a.G + g) * a.coef_gen_stride;
         *reinterpret_cast<uint4*>(out + (uint64_t)a.max_rows * 16) = make_uint4(0, 0, 0, 0);
     }
-    if (status == 0 && e > 0) {
+    // Rows by offset: 48-byte pair records over the accepted slots only, in
+    // arrival order (slot_col marks them once the matrix is built): accepted
+    // row t sits in pair t / 2, its offset and length in the pair's first 16
+    // bytes and its record behind them.  Rows at and after the accepted count
+    // are zero records of length 0 at the last accepted row's offset, also
+    // for a generation with nothing to recover, so every lane of
+    // k_combine_rows_at finds a readable unit.
+    uint32_t at_bound = 0;
+    if (AT) {
+        const uint32_t* ro = a.row_off + (uint64_t)g * a.max_rows;
+        const uint32_t* rl = a.row_len + (uint64_t)g * a.max_rows;
+        const uint32_t nrec = 2 * ((min(k, a.max_rows) + 1) / 2 + 1);
+        const uint32_t nb = (status == 0 && e > 0) ? bound : 0;
+        const uint32_t last_off = nb ? ro[nb - 1] : 0;   // slot bound - 1 is accepted
+        uint32_t mn = 0xFFFFFFFFu;
+        for (uint32_t s0 = 0; s0 < nb; s0 += 64) {
+            const uint32_t s = s0 + lane;
+            const uint32_t cl = s < nb ? L.slot_col[s] : 0xFFFF;
+            const uint64_t ba = __ballot(cl != 0xFFFF);
+            if (cl != 0xFFFF) {
+                const uint32_t t = at_bound + __popcll(ba & lt_mask);
+                const uint32_t off = ro[s], len = rl[s];
+                mn = min(mn, len);
+                for (uint32_t pass = 0; pass < a.passes; ++pass) {
+                    uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+                    for (int q = 0; q < 16; ++q) {
+                        const uint32_t m = pass * 16 + q;
+                        const uint32_t v = m < e ? L.M[m * W + cl] : 0u;
+                        w[q >> 2] |= v << (8 * (q & 3));
+                    }
+                    uint8_t* pair = a.coef_out + ((uint64_t)pass * a.G + g) * a.coef_gen_stride +
+                                    (uint64_t)(t >> 1) * kPairRecBytes;
+                    reinterpret_cast<uint32_t*>(pair)[t & 1] = off;
+                    reinterpret_cast<uint32_t*>(pair)[2 + (t & 1)] = len;
+                    *reinterpret_cast<uint4*>(pair + 16 + (t & 1) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+            }
+            at_bound += __popcll(ba);
+        }
+        for (uint32_t t = at_bound + lane; t < nrec; t += 64) {
+            for (uint32_t pass = 0; pass < a.passes; ++pass) {
+                uint8_t* pair = a.coef_out + ((uint64_t)pass * a.G + g) * a.coef_gen_stride +
+                                (uint64_t)(t >> 1) * kPairRecBytes;
+                reinterpret_cast<uint32_t*>(pair)[t & 1] = last_off;
+                reinterpret_cast<uint32_t*>(pair)[2 + (t & 1)] = 0;
+                *reinterpret_cast<uint4*>(pair + 16 + (t & 1) * 16) = make_uint4(0, 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor(mn, o, 64));
+        if (lane == 0) a.min_len[g] = at_bound ? mn : 0;
+        if (a.src_slot)
+            for (uint32_t i = lane; i < k; i += 64)
+                a.src_slot[(uint64_t)g * k + i] = status == 0 ? L.sys_slot[i] : (uint16_t)0xFFFF;
+        if (status == 0 && e > 0)
+            for (uint32_t m = lane; m < e; m += 64) a.rec_index[(uint64_t)g * emax + m] = L.emap[m];
+    } else if (status == 0 && e > 0) {
         for (uint32_t pass = 0; pass < a.passes; ++pass) {
             uint8_t* out = a.coef_out + ((uint64_t)pass * a.G + g) * a.coef_gen_stride;
             for (uint32_t s = lane; s < bound; s += 64) {
@@ -663,7 +729,7 @@ __global__ void __launch_bounds__(64) k_decode_prepare(PrepareArgs a) {
     if (lane == 0) {
         a.status[g] = status;
         a.n_out[g] = status == 0 ? e : 0;
-        a.bound[g] = status == 0 ? bound : 0;
+        a.bound[g] = AT ? at_bound : (status == 0 ? bound : 0);
     }
 }
 
@@ -1447,13 +1513,24 @@ hipError_t launch_decode_prepare(const PrepareArgs& a, hipStream_t st) {
     const size_t lds = prepare_lds_bytes(a.k, a.e_lds, a.max_rows);
     static bool attr_done = false;
     if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_prepare),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_prepare<false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_decode_prepare<true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         attr_done = true;
     }
     if (a.G == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_decode_prepare, dim3(a.G), dim3(64), lds, st, a);
+    if (a.row_off) {
+        // rows by offset: pair records, and the accepted rows must fit them
+        if (!a.row_len || !a.min_len || (a.src_gen_stride & 15) || (a.coef_gen_stride & 15) ||
+            a.coef_gen_stride < ((uint64_t)((a.k < a.max_rows ? a.k : a.max_rows) + 1) / 2 + 1) * kPairRecBytes)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_decode_prepare<true>, dim3(a.G), dim3(64), lds, st, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k_decode_prepare<false>, dim3(a.G), dim3(64), lds, st, a);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // qf_relay.hip -- a relay step that recodes straight from the received frame
 // slots: qf_parse_frame_headers_dev leaves every payload in
 // its slot and describes a row as (offset, length); qf_recode_frames_dev is
-// qf_recode_batch over rows given that way.
+// qf_recode_batch over rows given that way, and qf_decode_frames_dev (DESIGN.md
+// 3.13) qf_decode_innovative_batch over them, with the same payload pass.
 //
 //  k_combine_rows_at  the recode's payload pass, k_combine_slots with the rows
 //                     read where they lie.  One lane per 16-byte unit of the
@@ -153,6 +154,11 @@ QF_DEV void rows_at_dispatch(const CombineRowsAtArgs& a, const uint32_t* tab256,
     else rows_at_item<R, false>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax);
 }
 
+// PERGEN (the decode's pass, a.n_out_gen): the output rows of this pass differ
+// per generation as in k_combine_slots: a lane whose generation has none
+// contributes bound 0, a wave without an output row skips the item before it
+// loads a row, and the unrolled width follows the wave's largest count.
+template <bool PERGEN>
 __global__ void __launch_bounds__(256, 3) k_combine_rows_at(CombineRowsAtArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t tab256[256 * 8];
     {
@@ -177,14 +183,27 @@ __global__ void __launch_bounds__(256, 3) k_combine_rows_at(CombineRowsAtArgs a)
         const uint32_t gen_off = (uint32_t)(g * a.coef_gen_stride);
         const uint32_t rem = a.L - u16;
         const uint32_t nbytes = rem < 16 ? rem : 16;
-        const uint32_t e_lane = active ? a.n_out : 0;
-        const uint32_t smax = wave_max_u32(a.bound[g]);
+        uint32_t e_lane = active ? a.n_out : 0;
+        uint32_t bound_lane = a.bound[g];
+        uint32_t jmax = a.n_out;
+        if (PERGEN) {
+            // (a shadow lane has the first lane's generation, so its count changes no maximum)
+            const uint32_t e = a.n_out_gen[g], lo = a.pass * 16;
+            const uint32_t ep = e > lo ? (e - lo < 16 ? e - lo : 16) : 0;
+            e_lane = active ? ep : 0;
+            if (ep == 0) bound_lane = 0;
+            jmax = wave_max_u32(ep);
+            if (jmax == 0) continue;
+        }
+        const uint32_t smax = wave_max_u32(bound_lane);
         const bool full = __all(u16 + 16 <= a.min_len[g]);
         // smax == 0: every generation of the wave is not QF_OK; the ragged
         // path then stores the zero rows without a load
-        if (a.n_out <= 4) rows_at_dispatch<4>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
-        else if (a.n_out <= 8) rows_at_dispatch<8>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
-        else if (a.n_out <= 12) rows_at_dispatch<12>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        if (jmax <= 4) rows_at_dispatch<4>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else if (jmax <= 8) rows_at_dispatch<8>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else if (jmax <= 12) rows_at_dispatch<12>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else if (PERGEN && jmax <= 13) rows_at_dispatch<13>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
+        else if (PERGEN && jmax <= 14) rows_at_dispatch<14>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
         else rows_at_dispatch<16>(a, tab256, srcp, outp, gen_off, u16, nbytes, e_lane, smax, full);
     }
 }
@@ -196,8 +215,9 @@ hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipSt
     if (a.n_out == 0 || a.n_out > 16 || a.max_rows == 0 || a.Lu == 0 || a.Lu != (a.L + 15) / 16 || (a.src_gen_stride & 15) || (a.coef_gen_stride & 15) ||
         a.coef_gen_stride < ((uint64_t)(a.max_rows + 1) / 2 + 1) * kPairRecBytes)
         return hipErrorInvalidValue;
+    const auto kern = a.n_out_gen ? k_combine_rows_at<true> : k_combine_rows_at<false>;
     int occ = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_combine_rows_at, 256, 0);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0);
     if (e != hipSuccess) return e;
     if (occ < 1) occ = 1;
     const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 1) * occ;
@@ -213,11 +233,12 @@ hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipSt
         c.coef += g0 * a.coef_gen_stride;
         c.bound += g0;
         c.min_len += g0;
+        if (c.n_out_gen) c.n_out_gen += g0;
         c.total_units = gn * a.Lu;
         const uint64_t waves = (c.total_units + 63) / 64;
         uint64_t blocks = (waves + 3) / 4;
         if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(k_combine_rows_at, dim3((uint32_t)blocks), dim3(256), 0, st, c);
+        hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, st, c);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -338,6 +359,118 @@ extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* s
         a.Lu = Lu;
         a.max_rows = max_rows;
         a.total_units = (uint64_t)G * Lu;
+        ev = qf::ctx_prof_begin(ctx, st);
+        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st));
+        qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");
+    }
+    return QF_OK;
+}
+
+// The receiver's step over the same row descriptions: k_rank_filter's flags as
+// the accept mask, k_decode_prepare with pair records over the accepted rows,
+// then ceil(min(k, r) / 16) passes of k_combine_rows_at with per-generation
+// output counts.
+extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const uint8_t* src,
+                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
+                                    const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* rec,
+                                    uint16_t* rec_index, uint32_t* n_rec, int32_t* status, uint32_t* rank,
+                                    uint8_t* innovative, uint16_t* src_slot) {
+    if (!ctx || !sh) return QF_EINVAL;
+    qf::ctx_clear_payload_split(ctx);   // as qf_decode_innovative_batch: they apply to qf_decode_batch only
+    const uint32_t k = sh->k, r = sh->r, L = sh->L, max_rows = sh->max_rows;
+    if (k == 0 || k > 256 || max_rows == 0 || max_rows > 1024 || L == 0 || sh->flags != 0 || sh->reserved != 0)
+        return QF_EINVAL;
+    const uint32_t e_max = k < r ? k : r;
+    if (e_max > 128 || sh->rec_row_stride < L) return QF_EINVAL;
+    if (G == 0) return QF_OK;
+    if (!src || !row_off || !row_len || !row_index || !row_coeffs || !n_rec || !status) return QF_EINVAL;
+    if (e_max && (!rec || !rec_index)) return QF_EINVAL;
+    if (!aligned16(src) || (sh->src_gen_stride & 15) || !aligned16(rec) || (sh->rec_row_stride & 15) ||
+        (sh->rec_gen_stride & 15))
+        return QF_EINVAL;
+    const uint32_t e_lds = k < 128 ? k : 128;
+    if (qf::prepare_lds_bytes(k, e_lds, max_rows) > 160 * 1024) return QF_EINVAL;
+    std::unique_lock<std::mutex> lk;
+    int s = qf::ctx_lock(ctx, lk);
+    if (s) return s;
+    hipStream_t st = qf::ctx_stream(ctx);
+    // workspace: pair records [pass][G][((min(k, max_rows) + 1) / 2 + 1) * 48] | bound[G] | min_len[G] |
+    // the filter's flags [G][max_rows] unless the caller takes them
+    const uint32_t passes = (e_max + 15) / 16;
+    const uint32_t max_acc = k < max_rows ? k : max_rows;
+    const uint64_t coef_gen_stride = ((uint64_t)(max_acc + 1) / 2 + 1) * qf::kPairRecBytes;
+    const size_t off_bound = round_up((size_t)(passes ? passes : 1) * G * coef_gen_stride, 256);
+    const size_t off_minlen = off_bound + round_up((size_t)G * 4, 256);
+    const size_t off_flags = off_minlen + round_up((size_t)G * 4, 256);
+    uint8_t* w = nullptr;
+    s = qf::ctx_work(ctx, innovative ? off_flags : off_flags + (size_t)G * max_rows, &w);
+    if (s) return s;
+    uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
+    uint32_t* d_minlen = reinterpret_cast<uint32_t*>(w + off_minlen);
+    qf::RankFilterArgs fa{};
+    fa.row_index = row_index;
+    fa.n_rows = n_rows;
+    fa.row_coeffs = row_coeffs;
+    fa.explog = qf::ctx_explog(ctx);
+    fa.innovative = innovative ? innovative : w + off_flags;
+    fa.rank = rank;
+    fa.status = nullptr;   // k_decode_prepare applies the same index rules and reports
+    fa.k = k;
+    fa.r = r;
+    fa.max_rows = max_rows;
+    fa.G = G;
+    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
+    QF_CHECK_HIP(qf::launch_rank_filter(fa, st));
+    qf::ctx_prof_end(ctx, st, ev, "k_rank_filter");
+    qf::PrepareArgs pa{};
+    pa.accept = fa.innovative;
+    pa.row_index = row_index;
+    pa.n_rows = n_rows;
+    pa.row_coeffs = row_coeffs;
+    pa.explog = qf::ctx_explog(ctx);
+    pa.coef_out = w;
+    pa.coef_gen_stride = coef_gen_stride;
+    pa.n_out = n_rec;
+    pa.bound = d_bound;
+    pa.rec_index = rec_index;
+    pa.status = status;
+    pa.k = k;
+    pa.e_max = e_max;
+    pa.e_lds = e_lds;
+    pa.rep_limit = 256;
+    pa.max_rows = max_rows;
+    pa.max_rows_pad = (max_rows + 7) & ~7u;
+    pa.passes = passes;
+    pa.G = G;
+    pa.row_off = row_off;
+    pa.row_len = row_len;
+    pa.min_len = d_minlen;
+    pa.src_slot = src_slot;
+    pa.src_gen_stride = sh->src_gen_stride;
+    pa.L = L;
+    ev = qf::ctx_prof_begin(ctx, st);
+    QF_CHECK_HIP(qf::launch_decode_prepare(pa, st));
+    qf::ctx_prof_end(ctx, st, ev, "k_decode_prepare");
+    const uint32_t Lu = (L + 15) / 16;
+    for (uint32_t p = 0; p < passes; ++p) {
+        qf::CombineRowsAtArgs a{};
+        a.src = src;
+        a.src_gen_stride = sh->src_gen_stride;
+        a.dst = rec + (uint64_t)p * 16 * sh->rec_row_stride;
+        a.dst_gen_stride = sh->rec_gen_stride;
+        a.dst_row_stride = sh->rec_row_stride;
+        a.coef = w + (uint64_t)p * G * coef_gen_stride;
+        a.coef_gen_stride = coef_gen_stride;
+        a.bound = d_bound;
+        a.min_len = d_minlen;
+        a.tab256 = qf::ctx_tab256(ctx);
+        a.n_out = 16;
+        a.L = L;
+        a.Lu = Lu;
+        a.max_rows = max_acc;   // the records hold the accepted rows only
+        a.total_units = (uint64_t)G * Lu;
+        a.n_out_gen = n_rec;
+        a.pass = p;
         ev = qf::ctx_prof_begin(ctx, st);
         QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st));
         qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");

@@ -608,6 +608,46 @@ def recode_frames(src, row_off, row_len, row_index, row_coeffs, out, out_coeffs,
         "recode_frames")
 
 
+def decode_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status, k: int, r: int,
+                  Lb: int, *, max_rows: int, src_gen_stride: int, rec_row_stride: int, rec_gen_stride: int, G: int,
+                  n_rows=None, rank=None, innovative=None, src_slot=None, ctx: Optional[Context] = None) -> None:
+    """qf_decode_frames_dev: decode_innovative_batch over rows that lie where
+    they were received (rows as recode_frames': what parse_frame_headers
+    leaves, with src = the frames and src_gen_stride = max_rows *
+    frame_stride).  rec, rec_index, n_rec, status, rank and innovative as
+    decode_innovative_batch's.  src_slot: optional [G, k] u16, for a QF_OK
+    generation the slot of the accepted systematic row of each source, 0xFFFF
+    for a recovered one (found in rec through rec_index)."""
+    em = min(k, r)
+    _need(src, G * src_gen_stride, "src")
+    _need(row_off, 4 * G * max_rows, "row_off")
+    _need(row_len, 4 * G * max_rows, "row_len")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, Lb), "rec")
+    _need(rec_index, 2 * G * em, "rec_index (min(k, r) entries per generation)")
+    _need(n_rec, 4 * G, "n_rec")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if rank is not None:
+        _need(rank, 4 * G, "rank")
+    if innovative is not None:
+        _need(innovative, G * max_rows, "innovative")
+    if src_slot is not None:
+        _need(src_slot, 2 * G * k, "src_slot")
+    ctx = ctx or default_context()
+    sh = L.DecodeFramesShape(k, r, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride)
+    check(L._lib().qf_decode_frames_dev(
+        ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
+        _ptr(rec) if rec is not None else None, _ptr(rec_index) if rec_index is not None else None,
+        _ptr(n_rec), _ptr(status),
+        _ptr(rank) if rank is not None else None,
+        _ptr(innovative) if innovative is not None else None,
+        _ptr(src_slot) if src_slot is not None else None), "decode_frames")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
