@@ -578,6 +578,115 @@ int qf_decode_frames_dev(qf_ctx *ctx, const qf_decode_frames_shape *shape, uint3
                          uint16_t *src_slot_dev);
 
 /* ---------------------------------------------------------------------------
+ * Streaming receive: generations that fill over many calls.  No reference
+ * counterpart.  The calls above start from an empty span and need all rows of
+ * a generation in one call; a receiver or relay that polls gets a few rows of
+ * many generations at a time.  Two pieces carry a generation from one poll to
+ * the next: a rank state that qf_rank_update_batch resumes from and writes
+ * back, and a row store that qf_store_append_dev fills with the rows the
+ * state took.
+ *
+ * Rank state.  Generation g's state is the qf_rank_state_bytes(k) bytes at
+ * state_dev + g * qf_rank_state_bytes(k); the buffer is the caller's and is
+ * 16-byte aligned.  All-zero bytes mean "nothing received": a generation is
+ * reset by zeroing its state (a memset; no library call).  The contents are
+ * private, only the size is part of the ABI.  Two calls that touch the same
+ * generation's state must be ordered: the same context, or a stream
+ * dependency between their contexts.
+ * ------------------------------------------------------------------------- */
+/* No reference counterpart.  Bytes of one generation's rank state: a multiple
+ * of 16, 0 for k outside 1..256.  Host only, no device. */
+size_t qf_rank_state_bytes(uint32_t k);
+
+/* No reference counterpart.  qf_rank_batch that resumes from state_dev:
+ * row_index_dev, n_rows_dev, row_coeffs_dev, innovative_dev, the vectors v(s),
+ * the index validity rules and the call-level errors are those of
+ * qf_rank_batch (state_dev is a required pointer and must be 16-byte aligned:
+ * QF_EINVAL).  Slot s of this call is innovative iff v(s) is not in the span
+ * of (the span the state holds) and v(0) .. v(s-1) of this call; rank_dev[g]
+ * is the rank afterwards, and the state afterwards holds the enlarged span.
+ * So the flags of every QF_OK update since the state was zero, concatenated in
+ * call order, and the last rank are what qf_rank_batch and qf_gf256_rank give
+ * for the concatenated slots in one call.  Calls on one state may differ in
+ * max_rows, in r and in whether row_coeffs_dev is given; k is recorded in the
+ * state.
+ * status_dev[g]: QF_OK; QF_EINVAL for a slot that breaks its "needs" -- the
+ * call's slots of that generation are then ignored as a whole: flags 0, the
+ * state byte for byte unchanged, rank_dev[g] the rank the state held; QF_EINVAL
+ * also for a state that is neither zero nor a valid state for this k (flags 0,
+ * rank 0, the state untouched).  Validity is decided from the state's 16-byte
+ * header (zero, or the tag, this k and counts within 0..k) and a range check
+ * of the stored pivot columns and unit-column map before any of them is used.
+ * A generation with no slot in the call (n = 0) costs a read of that header:
+ * its flags are zeroed, rank_dev / status_dev are written, the state is not.
+ * The state is written only when the rank grew. */
+int qf_rank_update_batch(qf_ctx *ctx, const qf_rank_shape *shape, uint32_t G,
+                         const uint16_t *row_index_dev, const uint32_t *n_rows_dev,
+                         const uint8_t *row_coeffs_dev, uint8_t *state_dev,
+                         uint8_t *innovative_dev, uint32_t *rank_dev, int32_t *status_dev);
+
+/* No reference counterpart.  Appends rows to a per-generation row store.  The
+ * inputs are what qf_parse_frame_headers_dev leaves: rows[g][s] = the
+ * row_len_dev[g*max_rows + s] bytes at src_dev + g*src_gen_stride +
+ * row_off_dev[g*max_rows + s], with row_index_dev, n_rows_dev (NULL: max_rows)
+ * and row_coeffs_dev (required).  take_dev (nullable): one byte per input slot
+ * at g*max_rows + s, nonzero = take the row; NULL takes every row.  It is the
+ * innovative_dev of qf_rank_update_batch.
+ * The taken rows of generation g are appended in arrival order at store slots
+ * c = store_n_dev[g], store_n_dev[g] + 1, ..:
+ *   payload      to store_dev + g*store_gen_stride + c*store_row_stride:
+ *                round_up(row_len, 16) bytes, those after row_len zero
+ *   store_off_dev[g*cap + c]    = c * store_row_stride
+ *   store_len_dev[g*cap + c], store_index_dev[g*cap + c] and the k bytes of
+ *   store_coeffs_dev at (g*cap + c)*k  copied from the row
+ * and store_n_dev[g] grows by the number of taken rows (the caller zeroes it
+ * when it resets the generation).
+ * The five store arrays with max_rows = cap and src_gen_stride =
+ * store_gen_stride are the inputs of qf_decode_frames_dev (any cap in
+ * 1..1024), and of qf_recode_frames_dev when cap <= 255, that call's max_rows
+ * limit: a store with cap = 256 can be decoded but not recoded.
+ * status_dev[g]: QF_OK; QF_EINVAL when n_rows_dev[g] > max_rows or a taken row
+ * has row_len > L, row_off % 16 != 0 or row_off + row_len > src_gen_stride
+ * (checked first); QF_ETOOSMALL when store_n_dev[g] + taken rows > cap.  A
+ * generation that is not QF_OK appends nothing: no store byte, no metadata
+ * entry and no count changes.  After such a failure the generation's rank
+ * state (which took the rows) and its store disagree, and the caller resets
+ * both.  With the outputs of qf_parse_frame_headers_dev and cap >= k it cannot
+ * happen.
+ * Reads: only aligned 16-byte units of a taken row that hold one of its bytes;
+ * the payload of a row that is not taken is never read.  Writes: nothing
+ * outside the appended rows' round_up(row_len, 16) bytes and their metadata
+ * entries; slots below the old count and at or above the new one are
+ * untouched.  src_dev must not overlap store_dev.
+ * Returns QF_EINVAL for k outside 1..256, L == 0, max_rows or cap outside
+ * 1..1024, flags or reserved != 0, a stride not a multiple of 16,
+ * store_row_stride < round_up(L, 16), store_gen_stride < cap *
+ * store_row_stride, cap * store_row_stride > 2^32 (the offsets are u32), a
+ * NULL required pointer (all but n_rows_dev and take_dev), src_dev or
+ * store_dev not 16-byte aligned.  G == 0 is QF_OK.
+ * Two kernels: k_store_prepare (one wave per generation: checks, slots,
+ * metadata, vectors) and k_store_rows (one lane per 16-byte unit). */
+typedef struct qf_store_shape {
+    uint32_t k;                /* generation size, 1..256 */
+    uint32_t L;                /* payload bytes per row at most, >= 1 */
+    uint32_t max_rows;         /* input slots per generation, 1..1024 */
+    uint32_t cap;              /* store slots per generation, 1..1024 (k is enough when take = innovative) */
+    uint32_t flags;            /* 0 */
+    uint32_t reserved;         /* 0 */
+    uint64_t src_gen_stride;   /* bytes of one generation's source region, % 16 == 0 */
+    uint64_t store_row_stride; /* % 16 == 0, >= round_up(L, 16) */
+    uint64_t store_gen_stride; /* % 16 == 0, >= cap * store_row_stride */
+} qf_store_shape;
+
+int qf_store_append_dev(qf_ctx *ctx, const qf_store_shape *shape, uint32_t G,
+                        const uint8_t *src_dev, const uint32_t *row_off_dev,
+                        const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                        const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                        const uint8_t *take_dev, uint8_t *store_dev, uint32_t *store_off_dev,
+                        uint32_t *store_len_dev, uint16_t *store_index_dev,
+                        uint8_t *store_coeffs_dev, uint32_t *store_n_dev, int32_t *status_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations
@@ -922,6 +1031,13 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
  * receiver sequence for rows under 2,017 bytes; the one above from there on):
  *   qf_parse_frame_headers_dev  then qf_decode_frames_dev with src_dev = frames_in,
  *                               src_gen_stride = max_rows * frame_stride
+ * Streaming receiver or relay, a few frames of many generations per poll:
+ *   qf_parse_frame_headers_dev  the poll's frames -> row_off, row_len, row_index, n_rows, row_coeffs
+ *   qf_rank_update_batch        the same rows against the generations' rank states -> innovative, rank
+ *   qf_store_append_dev         take_dev = innovative: the new rows join the generations' stores
+ * and, once rank_dev[g] reaches k (a relay may recode sooner):
+ *   qf_decode_frames_dev        over the store arrays, max_rows = cap, src_gen_stride = store_gen_stride
+ *   qf_recode_frames_dev        the same at a relay (cap <= 255)
  * The intermediate rows belong to the caller.
  * ------------------------------------------------------------------------- */
 /* No reference counterpart (a layout rule): P = round_up(3 + k, 16) for k in

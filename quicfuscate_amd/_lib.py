@@ -86,6 +86,14 @@ class DecodeFramesShape(ctypes.Structure):
     ]
 
 
+class StoreShape(ctypes.Structure):
+    """qf_store_shape (append to a streaming receiver's row store)."""
+    _fields_ = [
+        ("k", _U32), ("L", _U32), ("max_rows", _U32), ("cap", _U32), ("flags", _U32), ("reserved", _U32),
+        ("src_gen_stride", _U64), ("store_row_stride", _U64), ("store_gen_stride", _U64),
+    ]
+
+
 class RankShape(ctypes.Structure):
     """qf_rank_shape (innovative-row filter)."""
     _fields_ = [("k", _U32), ("r", _U32), ("max_rows", _U32), ("flags", _U32)]
@@ -219,6 +227,10 @@ _SIGS = {
                                   _P, _P, _P, _P]),
     "qf_decode_frames_dev": (_I, [_P, ctypes.POINTER(DecodeFramesShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                   _P, _P, _P, _P]),
+    "qf_rank_state_bytes": (_SZ, [_U32]),
+    "qf_rank_update_batch": (_I, [_P, ctypes.POINTER(RankShape), _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_store_append_dev": (_I, [_P, ctypes.POINTER(StoreShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                 _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

@@ -29,7 +29,7 @@ LIB = OUT_DIR / "libqf_fec.so"
 LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
-           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip"]
+           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -428,7 +428,7 @@ def build(verbose: bool = False) -> Path:
             s: ex.submit(_compile, s, build_dir,
                          ["-Rpass-analysis=kernel-resource-usage"]
                          if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip", "qf_wire.hip",
-                                  "qf_relay.hip")
+                                  "qf_relay.hip", "qf_store.hip")
                          else [])
             for s in SOURCES
         }
@@ -449,8 +449,12 @@ def build(verbose: bool = False) -> Path:
                         print(f"  {n}: {u}")
             if s == "qf_rank.hip":
                 # k_rank_filter keeps the incoming vector in registers and the
-                # basis in LDS: no scratch
+                # basis in LDS: no scratch, in the one-call
+                # instantiations (1 .. 4 columns per lane) and in the four that
+                # resume from a rank state
                 ru = _check_no_scratch(err)
+                if sum("k_rank_filter" in n for n in ru) != 8:
+                    raise RuntimeError(f"k_rank_filter instantiations missing: {ru}")
                 if any(u.get("ScratchSize", 0) for u in ru.values()):
                     raise RuntimeError(f"k_rank_filter uses scratch: {ru}")
                 if verbose:
@@ -478,6 +482,16 @@ def build(verbose: bool = False) -> Path:
                 new = {n: u for n, u in ru.items() if "k_combine_rows_at" in n}
                 if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
                     raise RuntimeError(f"k_combine_rows_at instantiations missing or using scratch: {ru}")
+                if verbose:
+                    for n, u in sorted(ru.items()):
+                        print(f"  {n}: {u}")
+            if s == "qf_store.hip":
+                # the row store's control and payload passes hold a few
+                # addresses and one 16-byte unit per lane: no scratch
+                ru = _check_no_scratch(err)
+                new = {n: u for n, u in ru.items() if "k_store_prepare" in n or "k_store_rows" in n}
+                if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
+                    raise RuntimeError(f"k_store_prepare / k_store_rows missing or using scratch: {ru}")
                 if verbose:
                     for n, u in sorted(ru.items()):
                         print(f"  {n}: {u}")

@@ -256,6 +256,15 @@ struct RankFilterArgs {
 size_t rank_filter_lds_bytes(uint32_t k);
 hipError_t launch_rank_filter(const RankFilterArgs& a, hipStream_t st);
 
+// The same walk resumed from and written back to a per-generation rank state
+// (qf_rank_update_batch): generation g's rank_state_bytes(k) bytes at state +
+// g * rank_state_bytes(k), all zero for "nothing received".
+struct RankUpdateArgs : RankFilterArgs {
+    uint8_t* state;
+};
+size_t rank_state_bytes(uint32_t k);   // 0 for k outside 1..256
+hipError_t launch_rank_update(const RankUpdateArgs& a, hipStream_t st);
+
 // One encoder window of a multi-connection send batch: the window's ring at
 // src + src_off (position i in slot (rot + i) % k), its repairs at
 // rep + rep_off, rows rep_row_stride apart.

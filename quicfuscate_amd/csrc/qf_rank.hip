@@ -32,6 +32,10 @@
 //                  column to the dword.  The products thus run over coded
 //                  slots and coded basis rows only; the walk stops when the
 //                  rank reaches k.
+//                  Its second form (qf_rank_update_batch) restores U, B and
+//                  piv from a per-generation rank state in HBM first and
+//                  writes them back when the rank grew, so a generation
+//                  fills over many calls.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -181,13 +185,62 @@ QF_DEV void rank_insert(const RankLds& L, uint32_t lane, uint32_t nb, uint32_t t
 
 size_t rank_filter_lds_bytes(uint32_t k) { return rank_hdr(k) + (size_t)k * rank_kp(k); }
 
-// NQ = ceil(k / 64) columns per lane
-template <int NQ>
-__global__ void __launch_bounds__(64) k_rank_filter(RankFilterArgs a) {
+// The rank state of one generation in HBM (qf_rank_update_batch): the span
+// k_rank_filter holds in LDS, without what a call rebuilds.
+//   0   magic, k, nu, nb (u32 each); sixteen zero bytes: nothing received
+//   16  U as a bit per column, four u64 (column c: bit c % 64 of word c / 64)
+//   48  piv[kc] bytes, the first nb valid
+//   48 + kc  B, a dword per (row group d, column c) at (d * k + c) * 4: rows
+//       4d .. 4d + 3 of column c, the dwords of Bt; consecutive lanes hold
+//       consecutive columns, so a row group is one coalesced run.  The first
+//       ceil(nb / 4) groups are valid.
+// colst and pivrow follow from U and piv; first, lfac, stage and later are
+// scratch of one call.
+template <bool STATE> struct RankArgsOf { typedef RankFilterArgs type; };
+template <> struct RankArgsOf<true> { typedef RankUpdateArgs type; };
+constexpr uint32_t kStateMagic = 0x53524651u;   // "QFRS"
+constexpr uint32_t kStateUnits = 16, kStatePiv = 48;
+__host__ __device__ inline uint32_t rank_state_basis(uint32_t k) { return kStatePiv + rank_kc(k); }
+__host__ __device__ inline uint32_t rank_state_size(uint32_t k) {
+    return rank_state_basis(k) + ((((k + 3) & ~3u) * k + 15) & ~15u);
+}
+
+// NQ = ceil(k / 64) columns per lane.  STATE: the span is resumed from and
+// written back to a.state (the arguments are RankUpdateArgs; timed as
+// k_rank_update); without it every added block drops out and the code is the
+// one-call filter's, instruction for instruction.
+template <int NQ, bool STATE>
+__global__ void __launch_bounds__(64) k_rank_filter(typename RankArgsOf<STATE>::type a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t g = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     const uint32_t k = a.k, mr = a.max_rows;
+    uint32_t nu0 = 0, nb0 = 0;   // what the state held; rank0 = nu0 + nb0
+    uint32_t rank0 = 0;
+    uint8_t* sg = nullptr;
+    if constexpr (STATE) {
+        // The header decides, before anything else is read: an idle generation
+        // (no slot in this call) and an invalid state cost these 16 bytes.
+        sg = a.state + (uint64_t)g * rank_state_size(k);
+        const uint4 h = *reinterpret_cast<const uint4*>(sg);
+        const bool empty = (h.x | h.y | h.z | h.w) == 0;
+        const bool valid = empty || (h.x == kStateMagic && h.y == k && h.z <= k && h.w <= k && h.z + h.w <= k);
+        const uint32_t n_in = a.n_rows ? min(a.n_rows[g], mr) : mr;
+        if (valid) {
+            nu0 = h.z;
+            nb0 = h.w;
+            rank0 = nu0 + nb0;
+        }
+        if (!valid || n_in == 0) {
+            if (a.innovative)
+                for (uint32_t s = lane; s < mr; s += 64) a.innovative[(uint64_t)g * mr + s] = 0;
+            if (lane == 0) {
+                if (a.rank) a.rank[g] = rank0;
+                if (a.status) a.status[g] = valid ? QF_OK : QF_EINVAL;
+            }
+            return;
+        }
+    }
     RankLds L;
     L.exp = lds;
     L.log = lds + 512;
@@ -232,7 +285,62 @@ __global__ void __launch_bounds__(64) k_rank_filter(RankFilterArgs a) {
     for (int q = 0; q < NQ; ++q) sysc[q] = lane + 64 * q < k ? L.later[lane + 64 * q] : 0u;
     const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
 
-    uint32_t nu = 0, nb = 0;   // unit rows, coded basis rows; rank = nu + nb
+    if constexpr (STATE) {
+        // Restore U, piv and the nb rows of B into the layout above.  A full
+        // span and a generation with a bad slot walk nothing and need none of it.
+        if (n && rank0 < k && rank0) {
+            const uint32_t ng = (nb0 + 3) / 4;
+            // piv first, range-checked before any of it is used as an index
+            bool badp = false;
+            const uint32_t* sp = reinterpret_cast<const uint32_t*>(sg + kStatePiv);
+            for (uint32_t d = lane; d < ng; d += 64) {
+                const uint32_t p4 = sp[d];
+#pragma unroll
+                for (uint32_t t = 0; t < 4; ++t)
+                    if (4 * d + t < nb0 && ((p4 >> (8 * t)) & 0xFF) >= k) badp = true;
+                reinterpret_cast<uint32_t*>(L.piv)[d] = p4;
+            }
+            // U: as many columns below k as the header counts
+            const uint64_t* su = reinterpret_cast<const uint64_t*>(sg + kStateUnits);
+            uint32_t cnt_u = 0;
+            bool unit[NQ];
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const uint64_t m = su[q];
+                if (64u * (q + 1) > k && (m >> (k - 64u * q))) badp = true;   // a column at or above k
+                unit[q] = (m >> lane) & 1;
+                cnt_u += (uint32_t)__popcll(m);
+            }
+            for (int q = NQ; q < 4; ++q)
+                if (su[q]) badp = true;
+            if (__any(badp) || cnt_u != nu0) {
+                status = QF_EINVAL;
+                n = 0;
+                nu0 = nb0 = rank0 = 0;
+            } else {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q)
+                    if (unit[q]) L.colst[lane + 64 * q] = (uint8_t)kColUnit;
+                __syncthreads();
+                for (uint32_t b = lane; b < nb0; b += 64) {
+                    const uint32_t c = L.piv[b];
+                    L.colst[c] = (uint8_t)kColCoded;
+                    L.pivrow[c] = (uint8_t)b;
+                }
+                const uint32_t* sb = reinterpret_cast<const uint32_t*>(sg + rank_state_basis(k));
+                for (uint32_t d = 0; d < ng; ++d) {
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const uint32_t col = lane + 64 * q;
+                        if (col < k) reinterpret_cast<uint32_t*>(L.Bt + col * L.kp)[d] = sb[d * k + col];
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+
+    uint32_t nu = nu0, nb = nb0;   // unit rows, coded basis rows; rank = nu + nb
     uint32_t s0 = 0;
     for (; s0 < n && nu + nb < k; s0 += 64) {
         const uint32_t cnt = min(64u, n - s0);
@@ -337,25 +445,60 @@ __global__ void __launch_bounds__(64) k_rank_filter(RankFilterArgs a) {
     }
     if (inn)
         for (uint32_t s = s0 + lane; s < mr; s += 64) inn[s] = 0;
+    if constexpr (STATE) {
+        // The span changes exactly when the rank does: a call that brought
+        // nothing new (and one that was ignored) leaves the state as it is.
+        if (status == QF_OK && nu + nb != rank0) {
+            __syncthreads();
+            const uint32_t ng = (nb + 3) / 4;
+            uint64_t* su = reinterpret_cast<uint64_t*>(sg + kStateUnits);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                uint64_t m = 0;
+                if (q < NQ) m = __ballot(lane + 64 * q < k && L.colst[lane + 64 * q] == kColUnit);
+                if (lane == 0) su[q] = m;
+            }
+            // (rows nb .. 4 ng - 1 of the last group were never written: zeros go out)
+            const uint32_t tail = nb & 3 ? (1u << (8 * (nb & 3))) - 1 : 0xFFFFFFFFu;
+            uint32_t* sp = reinterpret_cast<uint32_t*>(sg + kStatePiv);
+            for (uint32_t d = lane; d < ng; d += 64)
+                sp[d] = reinterpret_cast<const uint32_t*>(L.piv)[d] & (d + 1 == ng ? tail : 0xFFFFFFFFu);
+            uint32_t* sb = reinterpret_cast<uint32_t*>(sg + rank_state_basis(k));
+            for (uint32_t d = 0; d < ng; ++d) {
+                const uint32_t keep = d + 1 == ng ? tail : 0xFFFFFFFFu;
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const uint32_t col = lane + 64 * q;
+                    if (col < k) sb[d * k + col] = reinterpret_cast<const uint32_t*>(L.Bt + col * L.kp)[d] & keep;
+                }
+            }
+            if (lane == 0) *reinterpret_cast<uint4*>(sg) = make_uint4(kStateMagic, k, nu, nb);
+        }
+    }
     if (lane == 0) {
         if (a.rank) a.rank[g] = nu + nb;
         if (a.status) a.status[g] = status;
     }
 }
 
-template <int NQ>
-static hipError_t launch_rank_filter_nq(const RankFilterArgs& a, size_t lds, hipStream_t st) {
+template <int NQ, class Args>
+static hipError_t launch_rank_nq(void (*kern)(Args), const Args& a, size_t lds, hipStream_t st) {
     if (lds > 64 * 1024) {   // k near 256: above the default dynamic LDS limit
-        static bool attr_done = false;
+        static bool attr_done = false;   // (one per kernel: NQ and Args name it)
         if (!attr_done) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rank_filter<NQ>),
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
             attr_done = true;
         }
     }
-    hipLaunchKernelGGL(k_rank_filter<NQ>, dim3(a.G), dim3(64), lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(a.G), dim3(64), lds, st, a);
     return hipGetLastError();
+}
+
+template <int NQ>
+static hipError_t launch_rank_filter_nq(const RankFilterArgs& a, size_t lds, hipStream_t st) {
+    return launch_rank_nq<NQ, RankFilterArgs>(k_rank_filter<NQ, false>, a, lds, st);
 }
 
 hipError_t launch_rank_filter(const RankFilterArgs& a, hipStream_t st) {
@@ -368,6 +511,22 @@ hipError_t launch_rank_filter(const RankFilterArgs& a, hipStream_t st) {
         case 2: return launch_rank_filter_nq<2>(a, lds, st);
         case 3: return launch_rank_filter_nq<3>(a, lds, st);
         default: return launch_rank_filter_nq<4>(a, lds, st);
+    }
+}
+
+size_t rank_state_bytes(uint32_t k) { return k >= 1 && k <= 256 ? rank_state_size(k) : 0; }
+
+hipError_t launch_rank_update(const RankUpdateArgs& a, hipStream_t st) {
+    if (a.G == 0) return hipSuccess;
+    if (a.k == 0 || a.k > 256 || a.max_rows == 0 || a.max_rows > 4096 || !a.state ||
+        (!a.row_coeffs && a.r && a.k + a.r > 256))
+        return hipErrorInvalidValue;
+    const size_t lds = rank_filter_lds_bytes(a.k);
+    switch ((a.k + 63) / 64) {
+        case 1: return launch_rank_nq<1, RankUpdateArgs>(k_rank_filter<1, true>, a, lds, st);
+        case 2: return launch_rank_nq<2, RankUpdateArgs>(k_rank_filter<2, true>, a, lds, st);
+        case 3: return launch_rank_nq<3, RankUpdateArgs>(k_rank_filter<3, true>, a, lds, st);
+        default: return launch_rank_nq<4, RankUpdateArgs>(k_rank_filter<4, true>, a, lds, st);
     }
 }
 
@@ -448,5 +607,40 @@ extern "C" int qf_rank_batch(qf_ctx* ctx, const qf_rank_shape* sh, uint32_t G, c
     hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
     QF_CHECK_HIP(qf::launch_rank_filter(fa, st));
     qf::ctx_prof_end(ctx, st, ev, "k_rank_filter");
+    return QF_OK;
+}
+
+extern "C" size_t qf_rank_state_bytes(uint32_t k) { return qf::rank_state_bytes(k); }
+
+extern "C" int qf_rank_update_batch(qf_ctx* ctx, const qf_rank_shape* sh, uint32_t G, const uint16_t* row_index,
+                                    const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* state,
+                                    uint8_t* innovative, uint32_t* rank, int32_t* status) {
+    if (!ctx || !sh) return QF_EINVAL;
+    const uint32_t k = sh->k, r = sh->r, max_rows = sh->max_rows;
+    if (k == 0 || k > 256 || max_rows == 0 || max_rows > 4096 || sh->flags != 0) return QF_EINVAL;
+    if (!row_coeffs && r && (uint64_t)k + r > 256) return QF_ERANGE;
+    if (G == 0) return QF_OK;
+    if (!row_index || !state || !rank || !status) return QF_EINVAL;
+    if (reinterpret_cast<uintptr_t>(state) & 15) return QF_EINVAL;
+    std::unique_lock<std::mutex> lk;
+    int s = qf::ctx_lock(ctx, lk);
+    if (s) return s;
+    hipStream_t st = qf::ctx_stream(ctx);
+    qf::RankUpdateArgs fa{};
+    fa.row_index = row_index;
+    fa.n_rows = n_rows;
+    fa.row_coeffs = row_coeffs;
+    fa.explog = qf::ctx_explog(ctx);
+    fa.innovative = innovative;
+    fa.rank = rank;
+    fa.status = status;
+    fa.k = k;
+    fa.r = r;
+    fa.max_rows = max_rows;
+    fa.G = G;
+    fa.state = state;
+    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
+    QF_CHECK_HIP(qf::launch_rank_update(fa, st));
+    qf::ctx_prof_end(ctx, st, ev, "k_rank_update");
     return QF_OK;
 }

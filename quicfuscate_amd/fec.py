@@ -648,6 +648,75 @@ def decode_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, 
         _ptr(src_slot) if src_slot is not None else None), "decode_frames")
 
 
+def rank_state_bytes(k: int) -> int:
+    """qf_rank_state_bytes: bytes of one generation's rank state (a multiple of
+    16; 0 for k outside 1..256).  Host only."""
+    return int(L._lib().qf_rank_state_bytes(int(k) & 0xFFFFFFFF))
+
+
+def rank_update_batch(row_index, state, rank, status, k: int, *, r: int = 0, max_rows: int, G: int, n_rows=None,
+                      row_coeffs=None, innovative=None, ctx: Optional[Context] = None) -> None:
+    """qf_rank_update_batch: rank_batch that resumes from and writes back a
+    per-generation rank state (state: G * rank_state_bytes(k) bytes, 16-byte
+    aligned, all zero = nothing received).  The flags of successive calls,
+    concatenated, and the last rank are those of one rank_batch over all the
+    slots.  A generation without a slot in the call is not written."""
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(state, G * rank_state_bytes(k), "state (rank_state_bytes(k) per generation)")
+    _need(rank, 4 * G, "rank")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if row_coeffs is not None:
+        _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    if innovative is not None:
+        _need(innovative, G * max_rows, "innovative")
+    ctx = ctx or default_context()
+    sh = L.RankShape(k, r, max_rows, 0)
+    check(L._lib().qf_rank_update_batch(
+        ctx.handle, ctypes.byref(sh), G, _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None,
+        _ptr(row_coeffs) if row_coeffs is not None else None,
+        _ptr(state),
+        _ptr(innovative) if innovative is not None else None,
+        _ptr(rank), _ptr(status)), "rank_update_batch")
+
+
+def store_append(src, row_off, row_len, row_index, row_coeffs, store, store_off, store_len, store_index,
+                 store_coeffs, store_n, status, k: int, Lb: int, *, max_rows: int, cap: int, src_gen_stride: int,
+                 store_row_stride: int, store_gen_stride: int, G: int, n_rows=None, take=None,
+                 ctx: Optional[Context] = None) -> None:
+    """qf_store_append_dev: the taken rows (take: [G, max_rows] bytes, None =
+    all; rank_update_batch's innovative) of what parse_frame_headers leaves are
+    appended to each generation's row store behind its store_n rows.  The five
+    store arrays with max_rows = cap and src_gen_stride = store_gen_stride are
+    the inputs of decode_frames and (cap <= 255) recode_frames."""
+    _need(src, G * src_gen_stride, "src")
+    _need(row_off, 4 * G * max_rows, "row_off")
+    _need(row_len, 4 * G * max_rows, "row_len")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need(store, _span(G, store_gen_stride, cap, store_row_stride, (Lb + 15) // 16 * 16), "store")
+    _need(store_off, 4 * G * cap, "store_off")
+    _need(store_len, 4 * G * cap, "store_len")
+    _need(store_index, 2 * G * cap, "store_index")
+    _need(store_coeffs, G * cap * k, "store_coeffs")
+    _need(store_n, 4 * G, "store_n")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G, "n_rows")
+    if take is not None:
+        _need(take, G * max_rows, "take")
+    ctx = ctx or default_context()
+    sh = L.StoreShape(k, Lb, max_rows, cap, 0, 0, src_gen_stride, store_row_stride, store_gen_stride)
+    check(L._lib().qf_store_append_dev(
+        ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
+        _ptr(take) if take is not None else None,
+        _ptr(store), _ptr(store_off), _ptr(store_len), _ptr(store_index), _ptr(store_coeffs), _ptr(store_n),
+        _ptr(status)), "store_append")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
