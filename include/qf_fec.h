@@ -687,6 +687,111 @@ int qf_store_append_dev(qf_ctx *ctx, const qf_store_shape *shape, uint32_t G,
                         uint8_t *store_coeffs_dev, uint32_t *store_n_dev, int32_t *status_dev);
 
 /* ---------------------------------------------------------------------------
+ * Streaming receive over a list of generations.  No reference counterpart.
+ * A poll touches few of a receiver's generations, and so should the step
+ * after it: qf_gen_select_dev builds a list of generations on the device,
+ * qf_decode_frames_sel_dev / qf_recode_frames_sel_dev run the store-side calls
+ * over the listed generations only, and qf_stream_reset_dev resets them.  No
+ * step needs the host to look at a device value.
+ * ------------------------------------------------------------------------- */
+/* No reference counterpart.  Generation g of 0..G-1 matches iff rank_dev[g] >=
+ * min_rank and (seen_dev == NULL or rank_dev[g] > seen_dev[g]).  The first
+ * min(matches, n_max) matching generations are written to sel_dev[0..] in
+ * ascending order of g, *n_sel_dev is that number and *n_match_dev (nullable)
+ * the number of all matches; sel_dev entries at and above *n_sel_dev are not
+ * written.  flags: 0 or QF_SELECT_MARK, which needs seen_dev and sets
+ * seen_dev[g] = rank_dev[g] for the selected generations only (a match beyond
+ * n_max is not marked, so it turns up in the next call); without it seen_dev
+ * is only read.  Receiver: min_rank = k and seen zeroed at reset list a
+ * generation once, in the poll in which it completes.  Relay: min_rank = 1
+ * lists a generation in every poll in which its rank grew.
+ * The list is deterministic (it does not depend on the order in which
+ * workgroups run).  Two launches (k_gen_select_count, k_gen_select_scatter), no
+ * workgroup waits for another.
+ * Returns QF_EINVAL for unknown flag bits, QF_SELECT_MARK without seen_dev,
+ * n_max == 0, G > 2^24, or a NULL required pointer (rank_dev when G > 0,
+ * sel_dev, n_sel_dev).  G == 0 writes *n_sel_dev = 0 (and *n_match_dev) and is
+ * QF_OK. */
+#define QF_SELECT_MARK 1u
+int qf_gen_select_dev(qf_ctx *ctx, uint32_t G, const uint32_t *rank_dev, uint32_t *seen_dev,
+                      uint32_t min_rank, uint32_t flags, uint32_t n_max,
+                      uint32_t *sel_dev, uint32_t *n_sel_dev, uint32_t *n_match_dev);
+
+/* A list of generations of source arrays that hold G_src of them.  Let
+ * n = min(*n_sel_dev, n_max) (n_sel_dev NULL: n_max).  Entries j < n are
+ * listed; one with sel_dev[j] >= G_src is invalid; entries n..n_max-1 are
+ * unused and their sel_dev values are never looked at.  Duplicates are legal
+ * and the list need not be sorted. */
+typedef struct qf_gen_sel {
+    const uint32_t *sel_dev;    /* n_max entries, generation numbers of the source arrays */
+    const uint32_t *n_sel_dev;  /* device count; nullable = n_max */
+    uint32_t n_max;             /* entries the call is sized for, >= 1 */
+    uint32_t G_src;             /* generations in the source arrays; an entry >= G_src is invalid */
+} qf_gen_sel;
+
+/* No reference counterpart.  qf_decode_frames_dev over a list.  The inputs
+ * (src_dev, row_off_dev, row_len_dev, row_index_dev, n_rows_dev, row_coeffs_dev,
+ * strides as in the shape) are the source arrays of sel->G_src generations and
+ * are indexed by the generation number sel_dev[j].  Every output is compact,
+ * indexed by the list position j in 0..n_max-1, and sized for n_max
+ * generations: rec_dev, rec_index_dev, n_rec_dev, status_dev, rank_dev,
+ * innovative_dev, src_slot_dev.
+ * A listed entry j with sel_dev[j] < G_src is written byte for byte as
+ * qf_decode_frames_dev writes generation j of a batch of n_max generations
+ * whose generation j has the metadata of source generation sel_dev[j] and a
+ * copy of its region.  An invalid entry gets status QF_EINVAL, n_rec 0, rank 0,
+ * no flags and src_slot 0xFFFF, and nothing is read through it.  An unused
+ * entry gets exactly what qf_decode_frames_dev writes for a generation with
+ * n_rows_dev[g] = 0.
+ * Reads: no payload byte of a generation that is not listed; within a listed
+ * one the read rules of qf_decode_frames_dev.  The sources are only read.
+ * Returns what qf_decode_frames_dev returns with n_max in the place of G, and
+ * QF_EINVAL for a NULL sel or sel_dev, n_max == 0 or G_src == 0.
+ * k_sel_gather (one wave per entry) copies the listed generations' metadata
+ * and vectors into compact arrays in the context workspace, the control
+ * kernels of qf_decode_frames_dev run over those, and k_combine_rows_at reads
+ * each entry's rows from the region of its source generation. */
+int qf_decode_frames_sel_dev(qf_ctx *ctx, const qf_decode_frames_shape *shape, const qf_gen_sel *sel,
+                             const uint8_t *src_dev, const uint32_t *row_off_dev,
+                             const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                             const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                             uint8_t *rec_dev, uint16_t *rec_index_dev, uint32_t *n_rec_dev,
+                             int32_t *status_dev, uint32_t *rank_dev, uint8_t *innovative_dev,
+                             uint16_t *src_slot_dev);
+
+/* No reference counterpart.  qf_recode_frames_dev over a list, inputs and
+ * compact outputs (out_dev, out_coeffs_dev, out_len_dev, status_dev) as in
+ * qf_decode_frames_sel_dev; mix_dev, or the splitmix stream of seed, is indexed
+ * by the list position j as well.  A listed entry with sel_dev[j] < G_src is
+ * written byte for byte as qf_recode_frames_dev writes generation j of the
+ * batch the list stands for.  An invalid entry is QF_EINVAL with zero rows,
+ * zero vectors and out_len 0, as that call's other QF_EINVAL generations, and
+ * nothing is read through it.  An unused entry gets status QF_ENOTREADY,
+ * out_len 0 and zero out_coeffs, but its m payload rows are NOT written (the
+ * dense call writes zero rows there): a caller that sizes n_max generously
+ * does not pay n_max * m * L bytes of stores.
+ * Returns what qf_recode_frames_dev returns with n_max in the place of G, and
+ * QF_EINVAL for a NULL sel or sel_dev, n_max == 0 or G_src == 0. */
+int qf_recode_frames_sel_dev(qf_ctx *ctx, const qf_recode_frames_shape *shape, const qf_gen_sel *sel,
+                             const uint8_t *src_dev, const uint32_t *row_off_dev,
+                             const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                             const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                             const uint8_t *mix_dev, uint64_t seed,
+                             uint8_t *out_dev, uint8_t *out_coeffs_dev, uint32_t *out_len_dev,
+                             int32_t *status_dev);
+
+/* No reference counterpart.  Resets the listed generations: for every listed
+ * entry with sel_dev[j] < G_src the qf_rank_state_bytes(k) state bytes of
+ * generation sel_dev[j], store_n_dev[sel_dev[j]] and seen_dev[sel_dev[j]] are
+ * zeroed, each where its pointer was given.  Nothing else is written; invalid
+ * and unused entries are skipped; duplicates are harmless.  One kernel
+ * (k_stream_reset), one lane per 16-byte unit of state.
+ * Returns QF_EINVAL for k outside 1..256, a NULL sel or sel_dev, n_max == 0,
+ * G_src == 0, all three pointers NULL, or state_dev not 16-byte aligned. */
+int qf_stream_reset_dev(qf_ctx *ctx, uint32_t k, const qf_gen_sel *sel, uint8_t *state_dev,
+                        uint32_t *store_n_dev, uint32_t *seen_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations

@@ -94,6 +94,14 @@ class StoreShape(ctypes.Structure):
     ]
 
 
+class GenSel(ctypes.Structure):
+    """qf_gen_sel (a device list of generations of arrays that hold G_src of them)."""
+    _fields_ = [("sel_dev", _P), ("n_sel_dev", _P), ("n_max", _U32), ("G_src", _U32)]
+
+
+QF_SELECT_MARK = 1   # qf_gen_select_dev flags: seen[g] = rank[g] for the selected generations
+
+
 class RankShape(ctypes.Structure):
     """qf_rank_shape (innovative-row filter)."""
     _fields_ = [("k", _U32), ("r", _U32), ("max_rows", _U32), ("flags", _U32)]
@@ -231,6 +239,12 @@ _SIGS = {
     "qf_rank_update_batch": (_I, [_P, ctypes.POINTER(RankShape), _U32, _P, _P, _P, _P, _P, _P, _P]),
     "qf_store_append_dev": (_I, [_P, ctypes.POINTER(StoreShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  _P, _P, _P]),
+    "qf_gen_select_dev": (_I, [_P, _U32, _P, _P, _U32, _U32, _U32, _P, _P, _P]),
+    "qf_decode_frames_sel_dev": (_I, [_P, ctypes.POINTER(DecodeFramesShape), ctypes.POINTER(GenSel), _P, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_recode_frames_sel_dev": (_I, [_P, ctypes.POINTER(RecodeFramesShape), ctypes.POINTER(GenSel), _P, _P, _P, _P,
+                                      _P, _P, _P, _U64, _P, _P, _P, _P]),
+    "qf_stream_reset_dev": (_I, [_P, _U32, ctypes.POINTER(GenSel), _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

@@ -29,7 +29,7 @@ LIB = OUT_DIR / "libqf_fec.so"
 LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
-           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip"]
+           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip", "qf_select.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -428,7 +428,7 @@ def build(verbose: bool = False) -> Path:
             s: ex.submit(_compile, s, build_dir,
                          ["-Rpass-analysis=kernel-resource-usage"]
                          if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip", "qf_wire.hip",
-                                  "qf_relay.hip", "qf_store.hip")
+                                  "qf_relay.hip", "qf_store.hip", "qf_select.hip")
                          else [])
             for s in SOURCES
         }
@@ -475,12 +475,13 @@ def build(verbose: bool = False) -> Path:
             if s == "qf_relay.hip":
                 # k_combine_rows_at keeps in-flight load destinations in
                 # registers like the other k_combine_* kernels (DESIGN.md
-                # 3.12): a spill would copy them before the data lands.  Two
-                # instantiations: the recoder's uniform output count and the
-                # decode's per-generation one
+                # 3.12): a spill would copy them before the data lands.  Three
+                # instantiations: the recoder's uniform output count, the
+                # decode's per-generation one and that one
+                # with a source map for the calls over a list
                 ru = _check_no_scratch(err)
                 new = {n: u for n, u in ru.items() if "k_combine_rows_at" in n}
-                if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
+                if len(new) != 3 or any(u.get("ScratchSize", 0) for u in new.values()):
                     raise RuntimeError(f"k_combine_rows_at instantiations missing or using scratch: {ru}")
                 if verbose:
                     for n, u in sorted(ru.items()):
@@ -492,6 +493,17 @@ def build(verbose: bool = False) -> Path:
                 new = {n: u for n, u in ru.items() if "k_store_prepare" in n or "k_store_rows" in n}
                 if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
                     raise RuntimeError(f"k_store_prepare / k_store_rows missing or using scratch: {ru}")
+                if verbose:
+                    for n, u in sorted(ru.items()):
+                        print(f"  {n}: {u}")
+            if s == "qf_select.hip":
+                # the list kernels hold a few counters or one 16-byte unit per
+                # lane: no scratch
+                ru = _check_no_scratch(err)
+                want = ("k_gen_select_count", "k_gen_select_scatter", "k_sel_gather", "k_stream_reset")
+                new = {n: u for n, u in ru.items() if any(w in n for w in want)}
+                if len(new) != 4 or any(u.get("ScratchSize", 0) for u in new.values()):
+                    raise RuntimeError(f"{' / '.join(want)} missing or using scratch: {ru}")
                 if verbose:
                     for n, u in sorted(ru.items()):
                         print(f"  {n}: {u}")

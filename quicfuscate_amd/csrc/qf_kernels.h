@@ -237,7 +237,43 @@ struct CombineRowsAtArgs {
     const uint32_t* n_out_gen = nullptr;
     uint32_t pass = 0;
 };
-hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st);
+// The calls over a list (qf_decode_frames_sel_dev, qf_recode_frames_sel_dev;
+// DESIGN.md 3.15): generation g of the batch reads the source region of
+// generation gen_map[g]; everything else stays indexed by g.  Needs n_out_gen.
+// Its own argument type, so the dense calls' kernels keep their arguments.
+struct CombineRowsAtMapArgs : CombineRowsAtArgs {
+    const uint32_t* gen_map;
+};
+hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st,
+                                  const uint32_t* gen_map = nullptr);
+
+// The batch a list stands for (k_sel_gather, qf_select.hip): one wave per list
+// entry j < n_max copies the first min(n_rows, max_rows) slots of generation
+// sel[j]'s row_off / row_len / row_index and vectors to entry j of the compact
+// arrays, with n_rows[j] the generation's and gen_map[j] = sel[j].  An entry at
+// or above min(*n_sel, n_max) gets n_rows 0, gen_map 0 and n_out 0 and is not
+// read; an entry >= G_src gets gen_map 0 and one slot of index 0xFFFF, length 0
+// with n_rows = invalid_n_rows, which the control kernels answer with QF_EINVAL
+// (k_rank_filter / k_decode_prepare for the index with invalid_n_rows = 1,
+// k_recode_prepare for invalid_n_rows > max_rows).
+struct SelGatherArgs {
+    const uint32_t* sel;
+    const uint32_t* n_sel;       // nullptr: n_max
+    const uint32_t* row_off;     // [G_src][max_rows]
+    const uint32_t* row_len;
+    const uint16_t* row_index;
+    const uint32_t* n_rows;      // [G_src] or nullptr (= max_rows)
+    const uint8_t* row_coeffs;   // [G_src][max_rows][k]
+    uint32_t* c_row_off;         // [n_max][max_rows]
+    uint32_t* c_row_len;
+    uint16_t* c_row_index;
+    uint32_t* c_n_rows;          // [n_max]
+    uint8_t* c_row_coeffs;       // [n_max][max_rows][k]
+    uint32_t* gen_map;           // [n_max]
+    uint32_t* n_out;             // [n_max] or nullptr: n_out_listed for a listed entry, 0 for an unused one
+    uint32_t n_max, G_src, k, max_rows, invalid_n_rows, n_out_listed;
+};
+hipError_t launch_sel_gather(const SelGatherArgs& a, hipStream_t st);
 
 // Innovative-row filter (qf_rank_batch, qf_decode_innovative_batch;
 // qf_rank.hip): one wave per generation walks the slots in arrival order and

@@ -26,6 +26,7 @@
 
 #include <mutex>
 #include <string>
+#include <type_traits>
 
 #include "qf_fec.h"
 #include "qf_kernels.h"
@@ -158,8 +159,13 @@ QF_DEV void rows_at_dispatch(const CombineRowsAtArgs& a, const uint32_t* tab256,
 // per generation as in k_combine_slots: a lane whose generation has none
 // contributes bound 0, a wave without an output row skips the item before it
 // loads a row, and the unrolled width follows the wave's largest count.
-template <bool PERGEN>
-__global__ void __launch_bounds__(256, 3) k_combine_rows_at(CombineRowsAtArgs a) {
+// MAPPED (the calls over a list, a.gen_map): the source region
+// of a lane's generation is region gen_map[g].  The records, counts and outputs
+// stay indexed by g, so this is the one place the listed generation's number
+// is needed, per lane: a wave spans several list entries when L < 1,024.
+template <bool PERGEN, bool MAPPED = false>
+__global__ void __launch_bounds__(256, 3)
+k_combine_rows_at(typename std::conditional<MAPPED, CombineRowsAtMapArgs, CombineRowsAtArgs>::type a) {
     __shared__ __attribute__((aligned(16))) uint32_t tab256[256 * 8];
     {
         const uint4* g = reinterpret_cast<const uint4*>(a.tab256);
@@ -178,7 +184,9 @@ __global__ void __launch_bounds__(256, 3) k_combine_rows_at(CombineRowsAtArgs a)
         const uint64_t g = f / a.Lu;
         const uint32_t u = (uint32_t)(f - g * a.Lu);
         const uint32_t u16 = u * 16;
-        const uint8_t* srcp = a.src + g * a.src_gen_stride + u16;
+        uint64_t gs = g;
+        if constexpr (MAPPED) gs = a.gen_map[g];
+        const uint8_t* srcp = a.src + gs * a.src_gen_stride + u16;
         uint8_t* outp = a.dst + g * a.dst_gen_stride + u16;
         const uint32_t gen_off = (uint32_t)(g * a.coef_gen_stride);
         const uint32_t rem = a.L - u16;
@@ -210,14 +218,15 @@ __global__ void __launch_bounds__(256, 3) k_combine_rows_at(CombineRowsAtArgs a)
 
 }  // namespace
 
-hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st) {
+hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipStream_t st, const uint32_t* gen_map) {
     if (a.total_units == 0) return hipSuccess;
     if (a.n_out == 0 || a.n_out > 16 || a.max_rows == 0 || a.Lu == 0 || a.Lu != (a.L + 15) / 16 || (a.src_gen_stride & 15) || (a.coef_gen_stride & 15) ||
-        a.coef_gen_stride < ((uint64_t)(a.max_rows + 1) / 2 + 1) * kPairRecBytes)
+        a.coef_gen_stride < ((uint64_t)(a.max_rows + 1) / 2 + 1) * kPairRecBytes || (gen_map && !a.n_out_gen))
         return hipErrorInvalidValue;
     const auto kern = a.n_out_gen ? k_combine_rows_at<true> : k_combine_rows_at<false>;
     int occ = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0);
+    hipError_t e = gen_map ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_combine_rows_at<true, true>, 256, 0)
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 256, 0);
     if (e != hipSuccess) return e;
     if (occ < 1) occ = 1;
     const uint64_t cap = (uint64_t)(num_cus > 0 ? num_cus : 1) * occ;
@@ -228,7 +237,7 @@ hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipSt
     for (uint64_t g0 = 0; g0 < G; g0 += g_max) {
         const uint64_t gn = G - g0 < g_max ? G - g0 : g_max;
         CombineRowsAtArgs c = a;
-        c.src += g0 * a.src_gen_stride;
+        if (!gen_map) c.src += g0 * a.src_gen_stride;   // (the map holds source generation numbers: src stays)
         c.dst += g0 * a.dst_gen_stride;
         c.coef += g0 * a.coef_gen_stride;
         c.bound += g0;
@@ -238,7 +247,12 @@ hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipSt
         const uint64_t waves = (c.total_units + 63) / 64;
         uint64_t blocks = (waves + 3) / 4;
         if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, st, c);
+        if (gen_map) {
+            CombineRowsAtMapArgs cm{c, gen_map + g0};
+            hipLaunchKernelGGL((k_combine_rows_at<true, true>), dim3((uint32_t)blocks), dim3(256), 0, st, cm);
+        } else {
+            hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(256), 0, st, c);
+        }
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -282,12 +296,35 @@ extern "C" int qf_parse_frame_headers_dev(qf_ctx* ctx, uint32_t k, uint32_t L, u
     return QF_OK;
 }
 
-extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint32_t G, const uint8_t* src,
-                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
-                                    const uint32_t* n_rows, const uint8_t* row_coeffs, const uint8_t* mix,
-                                    uint64_t seed, uint8_t* out, uint8_t* out_coeffs, uint32_t* out_len,
-                                    int32_t* status) {
-    if (!ctx || !sh) return QF_EINVAL;
+// The arrays of k_sel_gather behind a dense call's workspace of `base` bytes:
+// one ctx_work allocation holds both (a second ctx_work call may move the first).
+struct SelWork {
+    size_t off, len, index, n_rows, map, n_out, coeffs, end;
+};
+static SelWork sel_work(size_t base, uint32_t n_max, uint32_t max_rows, uint32_t k) {
+    SelWork w;
+    const size_t slots = (size_t)n_max * max_rows;
+    w.off = round_up(base, 256);
+    w.len = w.off + round_up(slots * 4, 256);
+    w.index = w.len + round_up(slots * 4, 256);
+    w.n_rows = w.index + round_up(slots * 2, 256);
+    w.map = w.n_rows + round_up((size_t)n_max * 4, 256);
+    w.n_out = w.map + round_up((size_t)n_max * 4, 256);
+    w.coeffs = w.n_out + round_up((size_t)n_max * 4, 256);
+    w.end = w.coeffs + slots * k;
+    return w;
+}
+static bool sel_ok(const qf_gen_sel* sel) { return sel && sel->sel_dev && sel->n_max != 0 && sel->G_src != 0; }
+
+// qf_recode_frames_dev (sel == nullptr), and qf_recode_frames_sel_dev over the
+// batch of G = sel->n_max generations that k_sel_gather makes of the list: the
+// same control kernel over the compact arrays, and the payload pass in its
+// per-generation-count form, so that an unused entry stores no row.
+static int recode_frames_run(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint32_t G, const qf_gen_sel* sel,
+                             const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                             const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                             const uint8_t* mix, uint64_t seed, uint8_t* out, uint8_t* out_coeffs, uint32_t* out_len,
+                             int32_t* status) {
     const uint32_t k = sh->k, L = sh->L, max_rows = sh->max_rows, m = sh->m;
     if (k == 0 || k > 255 || max_rows == 0 || max_rows > 255 || m == 0 || m > 64 || L == 0 || sh->flags != 0 ||
         sh->reserved != 0)
@@ -309,10 +346,47 @@ extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* s
     const size_t off_bound = off_nout + round_up((size_t)G * 4, 256);
     const size_t off_minlen = off_bound + round_up((size_t)G * 4, 256);
     uint8_t* w = nullptr;
-    s = qf::ctx_work(ctx, off_minlen + (size_t)G * 4, &w);
+    const size_t dense_bytes = off_minlen + (size_t)G * 4;
+    const SelWork sw = sel ? sel_work(dense_bytes, G, max_rows, k) : SelWork{};
+    s = qf::ctx_work(ctx, sel ? sw.end : dense_bytes, &w);
     if (s) return s;
     uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
     uint32_t* d_minlen = reinterpret_cast<uint32_t*>(w + off_minlen);
+    const uint32_t* gen_map = nullptr;
+    const uint32_t* n_out_gen = nullptr;
+    if (sel) {
+        qf::SelGatherArgs ga{};
+        ga.sel = sel->sel_dev;
+        ga.n_sel = sel->n_sel_dev;
+        ga.row_off = row_off;
+        ga.row_len = row_len;
+        ga.row_index = row_index;
+        ga.n_rows = n_rows;
+        ga.row_coeffs = row_coeffs;
+        ga.c_row_off = reinterpret_cast<uint32_t*>(w + sw.off);
+        ga.c_row_len = reinterpret_cast<uint32_t*>(w + sw.len);
+        ga.c_row_index = reinterpret_cast<uint16_t*>(w + sw.index);
+        ga.c_n_rows = reinterpret_cast<uint32_t*>(w + sw.n_rows);
+        ga.c_row_coeffs = w + sw.coeffs;
+        ga.gen_map = reinterpret_cast<uint32_t*>(w + sw.map);
+        ga.n_out = reinterpret_cast<uint32_t*>(w + sw.n_out);
+        ga.n_max = G;
+        ga.G_src = sel->G_src;
+        ga.k = k;
+        ga.max_rows = max_rows;
+        ga.invalid_n_rows = 0xFFFFFFFFu;   // n_rows > max_rows: k_recode_prepare's QF_EINVAL
+        ga.n_out_listed = m;
+        hipEvent_t evg = qf::ctx_prof_begin(ctx, st);
+        QF_CHECK_HIP(qf::launch_sel_gather(ga, st));
+        qf::ctx_prof_end(ctx, st, evg, "k_sel_gather");
+        row_off = ga.c_row_off;
+        row_len = ga.c_row_len;
+        row_index = ga.c_row_index;
+        n_rows = ga.c_n_rows;
+        row_coeffs = ga.c_row_coeffs;
+        gen_map = ga.gen_map;
+        n_out_gen = ga.n_out;
+    }
     qf::RecodePrepareArgs pa{};
     pa.row_index = row_index;
     pa.n_rows = n_rows;
@@ -359,23 +433,49 @@ extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* s
         a.Lu = Lu;
         a.max_rows = max_rows;
         a.total_units = (uint64_t)G * Lu;
+        if (sel) {
+            a.n_out = 16;   // the per-generation count decides: m for a listed entry, 0 for an unused one
+            a.n_out_gen = n_out_gen;
+            a.pass = p;
+        }
         ev = qf::ctx_prof_begin(ctx, st);
-        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st));
+        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st, gen_map));
         qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");
     }
     return QF_OK;
+}
+
+extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint32_t G, const uint8_t* src,
+                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
+                                    const uint32_t* n_rows, const uint8_t* row_coeffs, const uint8_t* mix,
+                                    uint64_t seed, uint8_t* out, uint8_t* out_coeffs, uint32_t* out_len,
+                                    int32_t* status) {
+    if (!ctx || !sh) return QF_EINVAL;
+    return recode_frames_run(ctx, sh, G, nullptr, src, row_off, row_len, row_index, n_rows, row_coeffs, mix, seed, out,
+                             out_coeffs, out_len, status);
+}
+
+extern "C" int qf_recode_frames_sel_dev(qf_ctx* ctx, const qf_recode_frames_shape* sh, const qf_gen_sel* sel,
+                                        const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                                        const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                                        const uint8_t* mix, uint64_t seed, uint8_t* out, uint8_t* out_coeffs,
+                                        uint32_t* out_len, int32_t* status) {
+    if (!ctx || !sh || !sel_ok(sel)) return QF_EINVAL;
+    return recode_frames_run(ctx, sh, sel->n_max, sel, src, row_off, row_len, row_index, n_rows, row_coeffs, mix, seed,
+                             out, out_coeffs, out_len, status);
 }
 
 // The receiver's step over the same row descriptions: k_rank_filter's flags as
 // the accept mask, k_decode_prepare with pair records over the accepted rows,
 // then ceil(min(k, r) / 16) passes of k_combine_rows_at with per-generation
 // output counts.
-extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const uint8_t* src,
-                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
-                                    const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* rec,
-                                    uint16_t* rec_index, uint32_t* n_rec, int32_t* status, uint32_t* rank,
-                                    uint8_t* innovative, uint16_t* src_slot) {
-    if (!ctx || !sh) return QF_EINVAL;
+// (sel as in recode_frames_run: the three control and payload kernels of the
+// dense call over the compact arrays, the payload pass reading through the map)
+static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const qf_gen_sel* sel,
+                             const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                             const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* rec,
+                             uint16_t* rec_index, uint32_t* n_rec, int32_t* status, uint32_t* rank,
+                             uint8_t* innovative, uint16_t* src_slot) {
     qf::ctx_clear_payload_split(ctx);   // as qf_decode_innovative_batch: they apply to qf_decode_batch only
     const uint32_t k = sh->k, r = sh->r, L = sh->L, max_rows = sh->max_rows;
     if (k == 0 || k > 256 || max_rows == 0 || max_rows > 1024 || L == 0 || sh->flags != 0 || sh->reserved != 0)
@@ -403,10 +503,43 @@ extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* s
     const size_t off_minlen = off_bound + round_up((size_t)G * 4, 256);
     const size_t off_flags = off_minlen + round_up((size_t)G * 4, 256);
     uint8_t* w = nullptr;
-    s = qf::ctx_work(ctx, innovative ? off_flags : off_flags + (size_t)G * max_rows, &w);
+    const size_t dense_bytes = innovative ? off_flags : off_flags + (size_t)G * max_rows;
+    const SelWork sw = sel ? sel_work(dense_bytes, G, max_rows, k) : SelWork{};
+    s = qf::ctx_work(ctx, sel ? sw.end : dense_bytes, &w);
     if (s) return s;
     uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
     uint32_t* d_minlen = reinterpret_cast<uint32_t*>(w + off_minlen);
+    const uint32_t* gen_map = nullptr;
+    if (sel) {
+        qf::SelGatherArgs ga{};
+        ga.sel = sel->sel_dev;
+        ga.n_sel = sel->n_sel_dev;
+        ga.row_off = row_off;
+        ga.row_len = row_len;
+        ga.row_index = row_index;
+        ga.n_rows = n_rows;
+        ga.row_coeffs = row_coeffs;
+        ga.c_row_off = reinterpret_cast<uint32_t*>(w + sw.off);
+        ga.c_row_len = reinterpret_cast<uint32_t*>(w + sw.len);
+        ga.c_row_index = reinterpret_cast<uint16_t*>(w + sw.index);
+        ga.c_n_rows = reinterpret_cast<uint32_t*>(w + sw.n_rows);
+        ga.c_row_coeffs = w + sw.coeffs;
+        ga.gen_map = reinterpret_cast<uint32_t*>(w + sw.map);
+        ga.n_max = G;
+        ga.G_src = sel->G_src;
+        ga.k = k;
+        ga.max_rows = max_rows;
+        ga.invalid_n_rows = 1;   // one slot of index 0xFFFF: the control kernels' QF_EINVAL, rank 0
+        hipEvent_t evg = qf::ctx_prof_begin(ctx, st);
+        QF_CHECK_HIP(qf::launch_sel_gather(ga, st));
+        qf::ctx_prof_end(ctx, st, evg, "k_sel_gather");
+        row_off = ga.c_row_off;
+        row_len = ga.c_row_len;
+        row_index = ga.c_row_index;
+        n_rows = ga.c_n_rows;
+        row_coeffs = ga.c_row_coeffs;
+        gen_map = ga.gen_map;
+    }
     qf::RankFilterArgs fa{};
     fa.row_index = row_index;
     fa.n_rows = n_rows;
@@ -472,8 +605,28 @@ extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* s
         a.n_out_gen = n_rec;
         a.pass = p;
         ev = qf::ctx_prof_begin(ctx, st);
-        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st));
+        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st, gen_map));
         qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");
     }
     return QF_OK;
+}
+
+extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const uint8_t* src,
+                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
+                                    const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* rec,
+                                    uint16_t* rec_index, uint32_t* n_rec, int32_t* status, uint32_t* rank,
+                                    uint8_t* innovative, uint16_t* src_slot) {
+    if (!ctx || !sh) return QF_EINVAL;
+    return decode_frames_run(ctx, sh, G, nullptr, src, row_off, row_len, row_index, n_rows, row_coeffs, rec, rec_index,
+                             n_rec, status, rank, innovative, src_slot);
+}
+
+extern "C" int qf_decode_frames_sel_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, const qf_gen_sel* sel,
+                                        const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                                        const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                                        uint8_t* rec, uint16_t* rec_index, uint32_t* n_rec, int32_t* status,
+                                        uint32_t* rank, uint8_t* innovative, uint16_t* src_slot) {
+    if (!ctx || !sh || !sel_ok(sel)) return QF_EINVAL;
+    return decode_frames_run(ctx, sh, sel->n_max, sel, src, row_off, row_len, row_index, n_rows, row_coeffs, rec,
+                             rec_index, n_rec, status, rank, innovative, src_slot);
 }

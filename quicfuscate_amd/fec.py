@@ -717,6 +717,129 @@ def store_append(src, row_off, row_len, row_index, row_coeffs, store, store_off,
         _ptr(status)), "store_append")
 
 
+QF_SELECT_MARK = L.QF_SELECT_MARK
+
+
+def gen_select(rank, sel, n_sel, *, G: int, min_rank: int, n_max: int, seen=None, mark: bool = False, n_match=None,
+               ctx: Optional[Context] = None) -> None:
+    """qf_gen_select_dev: the first n_max generations g of 0..G-1 with rank[g]
+    >= min_rank and (seen is None or rank[g] > seen[g]) go to sel[0..] in
+    ascending order, their number to n_sel[0] and the number of all matches to
+    n_match[0].  mark: seen[g] = rank[g] for the selected generations."""
+    _need(sel, 4 * n_max, "sel")
+    _need(n_sel, 4, "n_sel")
+    if G:
+        _need(rank, 4 * G, "rank")
+    if seen is not None:
+        _need(seen, 4 * G, "seen")
+    if n_match is not None:
+        _need(n_match, 4, "n_match")
+    ctx = ctx or default_context()
+    check(L._lib().qf_gen_select_dev(
+        ctx.handle, G, _ptr(rank) if rank is not None else None, _ptr(seen) if seen is not None else None,
+        min_rank, QF_SELECT_MARK if mark else 0, n_max, _ptr(sel), _ptr(n_sel),
+        _ptr(n_match) if n_match is not None else None), "gen_select")
+
+
+def _gen_sel(sel, n_sel, n_max: int, G_src: int) -> "L.GenSel":
+    _need(sel, 4 * n_max, "sel")
+    if n_sel is not None:
+        _need(n_sel, 4, "n_sel")
+    return L.GenSel(_ptr(sel), _ptr(n_sel) if n_sel is not None else None, n_max, G_src)
+
+
+def decode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status,
+                      k: int, r: int, Lb: int, *, n_max: int, G_src: int, max_rows: int, src_gen_stride: int,
+                      rec_row_stride: int, rec_gen_stride: int, n_rows=None, rank=None, innovative=None,
+                      src_slot=None, ctx: Optional[Context] = None) -> None:
+    """qf_decode_frames_sel_dev: decode_frames over the generations sel[0 ..
+    min(n_sel[0], n_max)) (n_sel None: n_max) of source arrays that hold G_src
+    generations.  Every output is compact: entry j of rec, rec_index, n_rec,
+    status, rank, innovative and src_slot belongs to generation sel[j]."""
+    em = min(k, r)
+    G = n_max
+    _need(src, G_src * src_gen_stride, "src")
+    _need(row_off, 4 * G_src * max_rows, "row_off")
+    _need(row_len, 4 * G_src * max_rows, "row_len")
+    _need(row_index, 2 * G_src * max_rows, "row_index")
+    _need(row_coeffs, G_src * max_rows * k, "row_coeffs")
+    _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, Lb), "rec")
+    _need(rec_index, 2 * G * em, "rec_index (min(k, r) entries per list entry)")
+    _need(n_rec, 4 * G, "n_rec")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G_src, "n_rows")
+    if rank is not None:
+        _need(rank, 4 * G, "rank")
+    if innovative is not None:
+        _need(innovative, G * max_rows, "innovative")
+    if src_slot is not None:
+        _need(src_slot, 2 * G * k, "src_slot")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    sh = L.DecodeFramesShape(k, r, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride)
+    check(L._lib().qf_decode_frames_sel_dev(
+        ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
+        _ptr(rec) if rec is not None else None, _ptr(rec_index) if rec_index is not None else None,
+        _ptr(n_rec), _ptr(status),
+        _ptr(rank) if rank is not None else None,
+        _ptr(innovative) if innovative is not None else None,
+        _ptr(src_slot) if src_slot is not None else None), "decode_frames_sel")
+
+
+def recode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, out, out_coeffs, status, k: int,
+                      m: int, Lb: int, *, n_max: int, G_src: int, max_rows: int, src_gen_stride: int,
+                      out_row_stride: int, out_gen_stride: int, n_rows=None, mix=None, seed: int = 0, out_len=None,
+                      ctx: Optional[Context] = None) -> None:
+    """qf_recode_frames_sel_dev: recode_frames over a list (as
+    decode_frames_sel).  out, out_coeffs, out_len, status and mix (or the
+    seeded stream) are indexed by the list position.  An unused entry gets
+    QF_ENOTREADY, out_len 0 and zero out_coeffs; its payload rows are not
+    written."""
+    G = n_max
+    _need(src, G_src * src_gen_stride, "src")
+    _need(row_off, 4 * G_src * max_rows, "row_off")
+    _need(row_len, 4 * G_src * max_rows, "row_len")
+    _need(row_index, 2 * G_src * max_rows, "row_index")
+    _need(row_coeffs, G_src * max_rows * k, "row_coeffs")
+    _need(out, _span(G, out_gen_stride, m, out_row_stride, Lb), "out")
+    _need(out_coeffs, G * m * k, "out_coeffs (m vectors of k bytes per list entry)")
+    _need(status, 4 * G, "status")
+    if n_rows is not None:
+        _need(n_rows, 4 * G_src, "n_rows")
+    if mix is not None:
+        _need(mix, G * m * max_rows, "mix")
+    if out_len is not None:
+        _need(out_len, 4 * G * m, "out_len")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    sh = L.RecodeFramesShape(k, Lb, max_rows, m, 0, 0, src_gen_stride, out_row_stride, out_gen_stride)
+    check(L._lib().qf_recode_frames_sel_dev(
+        ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
+        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
+        _ptr(mix) if mix is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _ptr(out), _ptr(out_coeffs), _ptr(out_len) if out_len is not None else None, _ptr(status)),
+        "recode_frames_sel")
+
+
+def stream_reset(sel, n_sel, k: int, *, n_max: int, G_src: int, state=None, store_n=None, seen=None,
+                 ctx: Optional[Context] = None) -> None:
+    """qf_stream_reset_dev: zeroes the rank state (rank_state_bytes(k) bytes),
+    store_n and seen of the listed generations, each where it is given."""
+    if state is not None:
+        _need(state, G_src * rank_state_bytes(k), "state (rank_state_bytes(k) per generation)")
+    if store_n is not None:
+        _need(store_n, 4 * G_src, "store_n")
+    if seen is not None:
+        _need(seen, 4 * G_src, "seen")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    check(L._lib().qf_stream_reset_dev(
+        ctx.handle, k, ctypes.byref(gs), _ptr(state) if state is not None else None,
+        _ptr(store_n) if store_n is not None else None, _ptr(seen) if seen is not None else None), "stream_reset")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
