@@ -20,6 +20,7 @@ import subprocess
 import sys
 import zlib
 from pathlib import Path
+from typing import NamedTuple
 
 PKG = Path(__file__).resolve().parent
 REPO = PKG.parent
@@ -138,6 +139,60 @@ def _check_no_scratch(remarks: str) -> dict[str, dict[str, int]]:
     bad = [n for n, u in usage.items() if "combine" in n and u.get("ScratchSize", 0) > 0]
     if bad:
         raise RuntimeError(f"register spill in asm-pipelined kernels (unsafe): {bad}")
+    return usage
+
+
+class _Rule(NamedTuple):
+    """What a source's kernel-resource-usage remarks must show: `count`
+    functions (None: any number) whose names contain one of `names`, and no
+    scratch in those functions, or with `every` in any function of the file."""
+    names: tuple[str, ...]
+    count: int | None
+    every: bool = False
+
+
+RESOURCE_RULES = {
+    # the asm-pipelined kernels keep in-flight load destinations in registers
+    "qf_kernels.hip": _Rule(("combine",), None),
+    # the control kernel of qf_recode_batch keeps its state in registers and
+    # LDS (DESIGN.md 3.9): no scratch
+    "qf_recode.hip": _Rule(("k_recode_prepare",), None, every=True),
+    # k_rank_filter keeps the incoming vector in registers and the basis in LDS
+    # (DESIGN.md 3.10): no scratch, in the one-call instantiations (1 .. 4
+    # columns per lane) and in the four that resume from a rank state
+    # (DESIGN.md 3.14)
+    "qf_rank.hip": _Rule(("k_rank_filter",), 8, every=True),
+    # the framing kernels of coded rows hold a few addresses and one 16-byte
+    # block per lane (DESIGN.md 3.11): no scratch
+    "qf_wire.hip": _Rule(("k_frame_rows", "k_parse_frames_coded", "k_parse_frame_headers"), 3),
+    # k_combine_rows_at keeps in-flight load destinations in registers like the
+    # other k_combine_* kernels (DESIGN.md 3.12): a spill would copy them before
+    # the data lands.  Three instantiations: the recoder's uniform output
+    # count, the decode's per-generation one (DESIGN.md 3.13) and that one with
+    # a source map for the calls over a list (DESIGN.md 3.15)
+    "qf_relay.hip": _Rule(("k_combine_rows_at",), 3),
+    # the row store's control and payload passes hold a few addresses and one
+    # 16-byte unit per lane (DESIGN.md 3.14): no scratch
+    "qf_store.hip": _Rule(("k_store_prepare", "k_store_rows"), 2),
+    # the list kernels hold a few counters or one 16-byte unit per lane
+    # (DESIGN.md 3.15): no scratch
+    "qf_select.hip": _Rule(("k_gen_select_count", "k_gen_select_scatter", "k_sel_gather", "k_stream_reset"), 4),
+}
+# the sources compiled with resource-usage remarks
+REMARK_SOURCES = ("qf_gf16_bs.hip", *RESOURCE_RULES)
+
+
+def _check_usage(src: str, remarks: str) -> dict[str, dict[str, int]]:
+    """The resource usage in one source's remarks, checked against its rule
+    (and, as for every source, against a spill in a k_combine_* kernel)."""
+    rule = RESOURCE_RULES[src]
+    usage = _check_no_scratch(remarks)
+    named = {n: u for n, u in usage.items() if any(w in n for w in rule.names)}
+    what = " / ".join(rule.names)
+    if rule.count is not None and len(named) != rule.count:
+        raise RuntimeError(f"{src}: {what}: {len(named)} of {rule.count} functions found: {usage}")
+    if any(u.get("ScratchSize", 0) for u in (usage if rule.every else named).values()):
+        raise RuntimeError(f"{src}: {what} using scratch: {usage}")
     return usage
 
 
@@ -426,10 +481,7 @@ def build(verbose: bool = False) -> Path:
     with cf.ThreadPoolExecutor(max_workers=4) as ex:
         futs = {
             s: ex.submit(_compile, s, build_dir,
-                         ["-Rpass-analysis=kernel-resource-usage"]
-                         if s in ("qf_kernels.hip", "qf_gf16_bs.hip", "qf_recode.hip", "qf_rank.hip", "qf_wire.hip",
-                                  "qf_relay.hip", "qf_store.hip", "qf_select.hip")
-                         else [])
+                         ["-Rpass-analysis=kernel-resource-usage"] if s in REMARK_SOURCES else [])
             for s in SOURCES
         }
         objs = []
@@ -438,77 +490,8 @@ def build(verbose: bool = False) -> Path:
             objs.append(obj)
             if s == "qf_gf16_bs.hip":
                 _check_gf16_bs(err)
-            if s == "qf_recode.hip":
-                # the control kernel of qf_recode_batch keeps its state in
-                # registers and LDS: no scratch
-                ru = _check_no_scratch(err)
-                if any(u.get("ScratchSize", 0) for u in ru.values()):
-                    raise RuntimeError(f"k_recode_prepare uses scratch: {ru}")
-                if verbose:
-                    for n, u in sorted(ru.items()):
-                        print(f"  {n}: {u}")
-            if s == "qf_rank.hip":
-                # k_rank_filter keeps the incoming vector in registers and the
-                # basis in LDS: no scratch, in the one-call
-                # instantiations (1 .. 4 columns per lane) and in the four that
-                # resume from a rank state
-                ru = _check_no_scratch(err)
-                if sum("k_rank_filter" in n for n in ru) != 8:
-                    raise RuntimeError(f"k_rank_filter instantiations missing: {ru}")
-                if any(u.get("ScratchSize", 0) for u in ru.values()):
-                    raise RuntimeError(f"k_rank_filter uses scratch: {ru}")
-                if verbose:
-                    for n, u in sorted(ru.items()):
-                        print(f"  {n}: {u}")
-            if s == "qf_wire.hip":
-                # the framing kernels of coded rows hold a few addresses and
-                # one 16-byte block per lane: no scratch
-                ru = _check_no_scratch(err)
-                new = {n: u for n, u in ru.items()
-                       if "k_frame_rows" in n or "k_parse_frames_coded" in n or "k_parse_frame_headers" in n}
-                if len(new) != 3 or any(u.get("ScratchSize", 0) for u in new.values()):
-                    raise RuntimeError("k_frame_rows / k_parse_frames_coded / k_parse_frame_headers missing or "
-                                       f"using scratch: {ru}")
-                if verbose:
-                    for n, u in sorted(ru.items()):
-                        print(f"  {n}: {u}")
-            if s == "qf_relay.hip":
-                # k_combine_rows_at keeps in-flight load destinations in
-                # registers like the other k_combine_* kernels (DESIGN.md
-                # 3.12): a spill would copy them before the data lands.  Three
-                # instantiations: the recoder's uniform output count, the
-                # decode's per-generation one and that one
-                # with a source map for the calls over a list
-                ru = _check_no_scratch(err)
-                new = {n: u for n, u in ru.items() if "k_combine_rows_at" in n}
-                if len(new) != 3 or any(u.get("ScratchSize", 0) for u in new.values()):
-                    raise RuntimeError(f"k_combine_rows_at instantiations missing or using scratch: {ru}")
-                if verbose:
-                    for n, u in sorted(ru.items()):
-                        print(f"  {n}: {u}")
-            if s == "qf_store.hip":
-                # the row store's control and payload passes hold a few
-                # addresses and one 16-byte unit per lane: no scratch
-                ru = _check_no_scratch(err)
-                new = {n: u for n, u in ru.items() if "k_store_prepare" in n or "k_store_rows" in n}
-                if len(new) != 2 or any(u.get("ScratchSize", 0) for u in new.values()):
-                    raise RuntimeError(f"k_store_prepare / k_store_rows missing or using scratch: {ru}")
-                if verbose:
-                    for n, u in sorted(ru.items()):
-                        print(f"  {n}: {u}")
-            if s == "qf_select.hip":
-                # the list kernels hold a few counters or one 16-byte unit per
-                # lane: no scratch
-                ru = _check_no_scratch(err)
-                want = ("k_gen_select_count", "k_gen_select_scatter", "k_sel_gather", "k_stream_reset")
-                new = {n: u for n, u in ru.items() if any(w in n for w in want)}
-                if len(new) != 4 or any(u.get("ScratchSize", 0) for u in new.values()):
-                    raise RuntimeError(f"{' / '.join(want)} missing or using scratch: {ru}")
-                if verbose:
-                    for n, u in sorted(ru.items()):
-                        print(f"  {n}: {u}")
-            if s == "qf_kernels.hip":
-                usage = _check_no_scratch(err)
+            if s in RESOURCE_RULES:
+                usage = _check_usage(s, err)
                 if verbose:
                     for n, u in sorted(usage.items()):
                         print(f"  {n}: {u}")

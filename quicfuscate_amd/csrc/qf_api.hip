@@ -60,8 +60,6 @@ const char* last_error_text() { return t_last_error; }
 }  // namespace qf
 
 
-static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
 struct EncTab {
     uint32_t* dev = nullptr;
     uint32_t k_pad = 0;
@@ -350,8 +348,6 @@ int prof_drain(qf_ctx* ctx) {
     ctx->prof_pending.clear();
     return QF_OK;
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // device copy of the Cauchy matrix (r x k), cached per (k, r)
 int small_coef_matrix(qf_ctx* ctx, uint32_t k, uint32_t r, const uint8_t** out) {
@@ -1089,6 +1085,20 @@ const uint8_t* ctx_explog(qf_ctx* ctx) { return ctx->d_explog; }
 hipError_t ctx_combine_payload(qf_ctx* ctx, const CombineSlotsArgs& a, hipStream_t st, std::string* name) {
     return combine_payload(ctx, a, pick_PD(ctx, QF_OPT_DECODE_PD, 1), st, name);
 }
+void prepare_common(qf_ctx* ctx, PrepareArgs& pa, const RowArrays& rows, uint32_t k, uint32_t e_max,
+                    uint32_t max_rows, uint32_t G) {
+    pa.row_index = rows.index;
+    pa.n_rows = rows.n_rows;
+    pa.row_coeffs = rows.coeffs;
+    pa.explog = ctx->d_explog;
+    pa.k = k;
+    pa.e_max = e_max;
+    pa.e_lds = std::min<uint32_t>(k, 128);
+    pa.max_rows = max_rows;
+    pa.max_rows_pad = (max_rows + 7) & ~7u;
+    pa.passes = (e_max + 15) / 16;
+    pa.G = G;
+}
 hipEvent_t ctx_prof_begin(qf_ctx* ctx, hipStream_t st) { return prof_begin(ctx, st); }
 void ctx_prof_end(qf_ctx* ctx, hipStream_t st, hipEvent_t ev, const std::string& name) {
     prof_end(ctx, st, ev, name);
@@ -1506,8 +1516,6 @@ int qf_ctx_set_payload_wait(qf_ctx* ctx, void* event) {
 // Every kernel runs on ctx->stream, so the decode workspace is reused in
 // stream order; a slot's next H2D follows its previous D2H on the same
 // stream, so the staging is never overwritten early.
-static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
 int qf_decode_batch_host(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const uint8_t* rows,
                          const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
                          uint8_t* rec, uint16_t* rec_index, uint32_t* n_rec, int32_t* status) {
@@ -1534,11 +1542,13 @@ int qf_decode_batch_host(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, con
     const uint64_t per_gen_in = sh->rows_gen_stride + 2ull * mr + 4 + (row_coeffs ? (uint64_t)mr * k : 0);
     uint64_t per = std::max<uint64_t>(1, (64ull << 20) / per_gen_in);
     per = std::min<uint64_t>(per, G);
-    // staging layout of one slot (256-B aligned parts)
-    const size_t o_rows = 0, o_idx = al256(per * sh->rows_gen_stride), o_n = o_idx + al256(per * mr * 2),
-                 o_coef = o_n + al256(per * 4), o_rec = o_coef + (row_coeffs ? al256(per * mr * k) : 0),
-                 o_ridx = o_rec + al256(per * sh->rec_gen_stride), o_nrec = o_ridx + al256(per * e_max * 2 + 2),
-                 o_st = o_nrec + al256(per * 4), total = o_st + al256(per * 4);
+    // staging layout of one slot (256-B aligned parts; the total, unlike a
+    // workspace's, is rounded up as well: it was, and it sizes the allocation)
+    qf::WorkLayout sl;
+    const size_t o_rows = sl.take(per * sh->rows_gen_stride), o_idx = sl.take(per * mr * 2), o_n = sl.take(per * 4),
+                 o_coef = sl.take(row_coeffs ? per * mr * k : 0), o_rec = sl.take(per * sh->rec_gen_stride),
+                 o_ridx = sl.take(per * e_max * 2 + 2), o_nrec = sl.take(per * 4), o_st = sl.take(per * 4),
+                 total = round_up(sl.size(), 256);
     {
         std::lock_guard<std::mutex> g(ctx->mu);
         if (total > ctx->dstage_bytes) {
@@ -1651,56 +1661,35 @@ static int decode_batch_impl(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G,
         return decode_cauchy_enc(ctx, sh, G, rows, row_index, n_rows, rec, rec_index, n_rec, status);
     const uint32_t passes = (e_max + 15) / 16;
     const uint64_t coef_gen_stride = ((uint64_t)max_rows + 1) * 16;
-    const size_t coef_bytes = (size_t)std::max<uint32_t>(passes, 1) * G * coef_gen_stride;
-    const size_t bound_off = round_up(coef_bytes, 256);
+    qf::WorkLayout wl;
+    const size_t coef_off = wl.take((size_t)std::max<uint32_t>(passes, 1) * G * coef_gen_stride);
+    const size_t bound_off = wl.take((size_t)G * 4);
     // (innovative decode: the filter's flags after the bounds, unless the caller takes them)
-    const size_t flags_off = round_up(bound_off + (size_t)G * 4, 256);
-    const size_t work_bytes = inv && !inv->innovative ? flags_off + (size_t)G * max_rows : bound_off + (size_t)G * 4;
-    s = grow_work(ctx, work_bytes);
+    const size_t flags_off = inv && !inv->innovative ? wl.take((size_t)G * max_rows) : 0;
+    s = grow_work(ctx, wl.size());
     if (s) return s;
-    uint8_t* d_coef = ctx->d_work;
+    uint8_t* d_coef = ctx->d_work + coef_off;
     uint32_t* d_bound = reinterpret_cast<uint32_t*>(ctx->d_work + bound_off);
-    qf::PrepareArgs pa{};
+    const qf::RowArrays ra{nullptr, nullptr, row_index, n_rows, row_coeffs};
+    uint8_t* accept = nullptr;
     if (inv) {
-        qf::RankFilterArgs fa{};
-        fa.row_index = row_index;
-        fa.n_rows = n_rows;
-        fa.row_coeffs = row_coeffs;
-        fa.explog = ctx->d_explog;
-        fa.innovative = inv->innovative ? inv->innovative : ctx->d_work + flags_off;
-        fa.rank = inv->rank;
-        fa.status = nullptr;   // k_decode_prepare applies the same index rules and reports
-        fa.k = k;
-        fa.r = r;
-        fa.max_rows = max_rows;
-        fa.G = G;
-        hipEvent_t evf = prof_begin(ctx, ctx->stream);
-        QF_CHECK_HIP(qf::launch_rank_filter(fa, ctx->stream));
-        prof_end(ctx, ctx->stream, evf, "k_rank_filter");
-        pa.accept = fa.innovative;
+        accept = inv->innovative ? inv->innovative : ctx->d_work + flags_off;
+        // (no status from the filter: k_decode_prepare applies the same index rules and reports)
+        QF_PROFILED(ctx, ctx->stream, "k_rank_filter",
+                    qf::launch_rank(ctx, ra, k, r, max_rows, G, nullptr, accept, inv->rank, nullptr, ctx->stream));
     }
-    pa.row_index = row_index;
-    pa.n_rows = n_rows;
-    pa.row_coeffs = row_coeffs;
-    pa.explog = ctx->d_explog;
+    qf::PrepareArgs pa{};
+    qf::prepare_common(ctx, pa, ra, k, e_max, max_rows, G);
+    pa.accept = accept;
     pa.coef_out = d_coef;
     pa.coef_gen_stride = coef_gen_stride;
     pa.n_out = n_rec;
     pa.bound = d_bound;
     pa.rec_index = rec_index;
     pa.status = status;
-    pa.k = k;
-    pa.e_max = e_max;
-    pa.e_lds = std::min<uint32_t>(k, 128);
     pa.rep_limit = row_coeffs ? 256 : r;
-    pa.max_rows = max_rows;
-    pa.max_rows_pad = (max_rows + 7) & ~7u;
-    pa.passes = passes;
-    pa.G = G;
     if (qf::prepare_lds_bytes(k, pa.e_lds, max_rows) > 160 * 1024) return QF_EINVAL;
-    hipEvent_t ev = prof_begin(ctx, ctx->stream);
-    QF_CHECK_HIP(qf::launch_decode_prepare(pa, ctx->stream));
-    prof_end(ctx, ctx->stream, ev, "k_decode_prepare");
+    QF_PROFILED(ctx, ctx->stream, "k_decode_prepare", qf::launch_decode_prepare(pa, ctx->stream));
     if (int gs = payload_gate(ctx, ctx->stream)) return gs;
     const uint32_t Lu = (L + 15) / 16;
     bool pm = false;   // every pass in one pass-major launch, as in decode_cauchy_syn
@@ -1757,10 +1746,9 @@ int qf_frame_batch_dev(qf_ctx* ctx, const qf_encode_shape* sh, uint32_t G, const
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    hipEvent_t ev = prof_begin(ctx, ctx->stream);
-    QF_CHECK_HIP(qf::launch_frame_batch(src, rep, *sh, G, frames, frame_stride, frame_len, ctx->d_explog,
-                                        ctx->num_cus, ctx->stream));
-    prof_end(ctx, ctx->stream, ev, "k_frame_batch");
+    QF_PROFILED(ctx, ctx->stream, "k_frame_batch",
+                qf::launch_frame_batch(src, rep, *sh, G, frames, frame_stride, frame_len, ctx->d_explog,
+                                       ctx->num_cus, ctx->stream));
     return QF_OK;
 }
 
@@ -1779,11 +1767,10 @@ int qf_parse_frames_dev(qf_ctx* ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    hipEvent_t ev = prof_begin(ctx, ctx->stream);
-    QF_CHECK_HIP(qf::launch_parse_frames(frames, frame_stride, frame_len, ids, n_frames, k, r, L, G, max_rows, rows,
-                                         row_stride, rows_gen_stride, row_index, n_rows, frame_status,
-                                         ctx->d_explog, ctx->stream));
-    prof_end(ctx, ctx->stream, ev, "k_parse_frames");
+    QF_PROFILED(ctx, ctx->stream, "k_parse_frames",
+                qf::launch_parse_frames(frames, frame_stride, frame_len, ids, n_frames, k, r, L, G, max_rows, rows,
+                                        row_stride, rows_gen_stride, row_index, n_rows, frame_status,
+                                        ctx->d_explog, ctx->stream));
     return QF_OK;
 }
 
@@ -1808,10 +1795,9 @@ int qf_frame_rows_dev(qf_ctx* ctx, const qf_frame_rows_shape* sh, uint32_t G, co
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    hipEvent_t ev = prof_begin(ctx, ctx->stream);
-    QF_CHECK_HIP(qf::launch_frame_rows(in_place ? nullptr : rows, row_index, n_rows, row_coeffs, row_len, *sh, G,
-                                       frames, frame_len, frame_off, ctx->d_explog, ctx->num_cus, ctx->stream));
-    prof_end(ctx, ctx->stream, ev, "k_frame_rows");
+    QF_PROFILED(ctx, ctx->stream, "k_frame_rows",
+                qf::launch_frame_rows(in_place ? nullptr : rows, row_index, n_rows, row_coeffs, row_len, *sh, G,
+                                      frames, frame_len, frame_off, ctx->d_explog, ctx->num_cus, ctx->stream));
     return QF_OK;
 }
 
@@ -1832,11 +1818,10 @@ int qf_parse_frames_coded_dev(qf_ctx* ctx, uint32_t k, uint32_t L, uint32_t G, u
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    hipEvent_t ev = prof_begin(ctx, ctx->stream);
-    QF_CHECK_HIP(qf::launch_parse_frames_coded(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
-                                               max_rows, rows, row_stride, rows_gen_stride, row_index, n_rows,
-                                               row_coeffs, row_len, frame_status, ctx->stream));
-    prof_end(ctx, ctx->stream, ev, "k_parse_frames_coded");
+    QF_PROFILED(ctx, ctx->stream, "k_parse_frames_coded",
+                qf::launch_parse_frames_coded(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
+                                              max_rows, rows, row_stride, rows_gen_stride, row_index, n_rows,
+                                              row_coeffs, row_len, frame_status, ctx->stream));
     return QF_OK;
 }
 

@@ -33,11 +33,10 @@
 #include <vector>
 
 #include "qf_fec.h"
+#include "qf_gf_dev.h"
 #include "qf_internal.h"
 
 namespace {
-
-#define QF_DEV __device__ __forceinline__
 
 constexpr uint32_t kOrder = 65535;  // multiplicative group order
 constexpr uint32_t kNoLog = 0xFFFF; // log of 0 (no product)
@@ -1097,11 +1096,9 @@ int launch_matvec(qf_ctx* ctx, hipStream_t st, Mv16Args& a, uint64_t G, const ch
             uint8_t* lr = nullptr;
             int s = qf::ctx_gf16_logrows(ctx, n * 16, &lr);
             if (s) return s;
-            hipEvent_t ev0 = qf::ctx_prof_begin(ctx, st);
-            hipLaunchKernelGGL(k_logify16, dim3(grid16(ctx, n)), dim3(kThreads16), 0, st, a, G,
-                               reinterpret_cast<uint16_t*>(lr));
-            QF_HIP(hipGetLastError());
-            qf::ctx_prof_end(ctx, st, ev0, "k_logify16");
+            QF_PROFILED(ctx, st, "k_logify16",
+                        qf::launch_kernel(k_logify16, dim3(grid16(ctx, n)), dim3(kThreads16), 0, st, a, G,
+                                          reinterpret_cast<uint16_t*>(lr)));
             a.in = lr;
             a.igs = (uint64_t)a.nin * a.Lu * 16;
             a.irs = (uint64_t)a.Lu * 16;
@@ -1275,10 +1272,8 @@ int qf_decode16_batch(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const 
         d.r = r;
         d.e_max = ew;
         d.max_rows = max_rows;
-        hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-        hipLaunchKernelGGL(k_decode16_prepare, dim3(G), dim3(256), 0, st, d);
-        QF_HIP(hipGetLastError());
-        qf::ctx_prof_end(ctx, st, ev, "k_decode16_prepare");
+        QF_PROFILED(ctx, st, "k_decode16_prepare",
+                    qf::launch_kernel(k_decode16_prepare, dim3(G), dim3(256), 0, st, d));
         Mv16Args c{};
         c.in = rows;
         c.igs = sh->rows_gen_stride;

@@ -242,10 +242,7 @@ int gf16_bs_encode(qf_ctx* ctx, hipStream_t st, uint32_t k, uint32_t r, uint32_t
     const uint64_t blocks = (a.total + 255) / 256;
     const uint64_t grid = (blocks + 7) / 8 * 8 * e->passes;
     if (grid > 0x7FFFFFFFull) return QF_ERANGE;
-    hipEvent_t ev = ctx_prof_begin(ctx, st);
-    hipLaunchKernelGGL(e->fn, dim3((uint32_t)grid), dim3(256), 0, st, a);
-    QF_CHECK_HIP(hipGetLastError());
-    ctx_prof_end(ctx, st, ev, e->name);
+    QF_PROFILED(ctx, st, e->name, qf::launch_kernel(e->fn, dim3((uint32_t)grid), dim3(256), 0, st, a));
     return QF_OK;
 }
 
@@ -285,10 +282,8 @@ int gf16_bs_syndromes(qf_ctx* ctx, hipStream_t st, uint32_t k, uint32_t r, uint3
     const uint64_t blocks = (a.total + 255) / 256;
     const uint64_t grid = (blocks + 7) / 8 * 8 * e->passes;
     if (grid > 0x7FFFFFFFull) return QF_ERANGE;
-    hipEvent_t ev = ctx_prof_begin(ctx, st);
-    hipLaunchKernelGGL(e->syn, dim3((uint32_t)grid), dim3(256), 0, st, a);
-    QF_CHECK_HIP(hipGetLastError());
-    ctx_prof_end(ctx, st, ev, e->syn_name);
+    QF_PROFILED(ctx, st, e->syn_name,
+                qf::launch_kernel(e->syn, dim3((uint32_t)grid), dim3(256), 0, st, a));
     return QF_OK;
 }
 

@@ -1,7 +1,10 @@
-// qf_gf_dev.h -- device helpers of the v_perm payload kernels, shared by
-// qf_kernels.hip (k_combine_uniform, k_combine_slots, ...) and qf_relay.hip
-// (k_combine_rows_at): the split-table multiply-add of gf256_tables.h, unit
-// loads and stores, the asm streaming load and the wave maximum.
+// qf_gf_dev.h -- device helpers shared by the .hip files.  For all of them:
+// QF_DEV (the one definition) and the unit loads and stores, among them the
+// masked row-unit load of qf_relay.hip and qf_store.hip.  For the v_perm
+// payload kernels of qf_kernels.hip (k_combine_uniform, k_combine_slots, ...)
+// and qf_relay.hip (k_combine_rows_at): the split-table multiply-add of
+// gf256_tables.h, the asm streaming load and the wave maximum.  Everything
+// here is inline device code: a file that uses none of it emits none of it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,6 +42,25 @@ QF_DEV uint4 load_unit(const uint8_t* p, uint32_t nb) {
         }
     }
     return r;
+}
+
+QF_DEV uint32_t low_bytes_mask(uint32_t nb) { return nb >= 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1; }
+
+// The unit at p of a row of len bytes, u16 = 16 * unit index: the bytes of the
+// unit at and after len are zero, and a unit without a valid byte is not loaded.
+QF_DEV uint4 load_row_unit(const uint8_t* p, uint32_t len, uint32_t u16) {
+    uint4 x = make_uint4(0, 0, 0, 0);
+    if (len > u16) {
+        x = *reinterpret_cast<const uint4*>(p);
+        const uint32_t v = len - u16;
+        if (v < 16) {
+            x.x &= low_bytes_mask(v);
+            x.y &= low_bytes_mask(v > 4 ? v - 4 : 0);
+            x.z &= low_bytes_mask(v > 8 ? v - 8 : 0);
+            x.w &= low_bytes_mask(v > 12 ? v - 12 : 0);
+        }
+    }
+    return x;
 }
 
 QF_DEV void store_unit(uint8_t* p, const uint4& v, uint32_t nb) {

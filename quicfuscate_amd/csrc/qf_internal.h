@@ -10,6 +10,9 @@
 
 #include "qf_fec.h"
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
 namespace qf {
 
 // Locks the context and makes its device current.
@@ -44,9 +47,50 @@ hipError_t ctx_combine_payload(qf_ctx* ctx, const CombineSlotsArgs& a, hipStream
 void ctx_clear_payload_split(qf_ctx* ctx);
 // The context's value of option `opt` (QF_OPT_*, qf_ctx_set_option).
 int64_t ctx_opt(qf_ctx* ctx, int opt);
-// qf_ctx_profile bracketing of a launch.
+// qf_ctx_profile bracketing of a launch (QF_PROFILED below).
 hipEvent_t ctx_prof_begin(qf_ctx* ctx, hipStream_t st);
 void ctx_prof_end(qf_ctx* ctx, hipStream_t st, hipEvent_t ev, const std::string& name);
+
+// The parts of one call's device workspace, each at a multiple of 256 bytes:
+// take() in layout order, then one ctx_work(size()) for all of them.
+struct WorkLayout {
+    size_t end = 0;
+    size_t take(size_t bytes) {
+        const size_t off = round_up(end, 256);
+        end = off + bytes;
+        return off;
+    }
+    size_t size() const { return end; }
+};
+
+// A batch's rows described where they lie: row s of generation g is len bytes
+// at off from the generation's source region, with its index and coefficient
+// vector ([G][max_rows] each, coeffs [G][max_rows][k]) and n_rows[G] (nullptr:
+// max_rows).  off / len are nullptr for the calls that read no payload.
+struct RowArrays {
+    const uint32_t* off;
+    const uint32_t* len;
+    const uint16_t* index;
+    const uint32_t* n_rows;
+    const uint8_t* coeffs;
+};
+
+// QF_LOCAL keeps a function that several translation units share out of the
+// library's dynamic symbols, so that the exported list stays what it was (the
+// older internals of this header predate it and are still exported).
+#define QF_LOCAL __attribute__((visibility("hidden")))
+// k_rank_filter over the rows, or with state != nullptr the walk resumed from
+// and written back to the rank states (k_rank_update).  (qf_rank.hip)
+QF_LOCAL hipError_t launch_rank(qf_ctx* ctx, const RowArrays& rows, uint32_t k, uint32_t r, uint32_t max_rows,
+                                uint32_t G, uint8_t* state, uint8_t* innovative, uint32_t* rank, int32_t* status,
+                                hipStream_t st);
+// The fields of k_decode_prepare's arguments that follow from the rows and the
+// shape alike for every caller: the row arrays, the tables, k, e_max, e_lds,
+// max_rows, max_rows_pad, passes and G.  The outputs, accept, coef_gen_stride,
+// rep_limit and the row_off group are set by the caller, by name.
+struct PrepareArgs;
+QF_LOCAL void prepare_common(qf_ctx* ctx, PrepareArgs& pa, const RowArrays& rows, uint32_t k, uint32_t e_max,
+                             uint32_t max_rows, uint32_t G);
 
 }  // namespace qf
 
@@ -233,3 +277,22 @@ const char* last_error_text();
         if (_e != hipSuccess) return qf::device_fail(__FILE__, __LINE__, _e);  \
     } while (0)
 
+// One launch under qf_ctx_profile: begin, the launch (an expression of type
+// hipError_t), its check, end under `name` (evaluated after the launch, so a
+// launch that picks its kernel may set it).  Returns from the calling function
+// on failure, with the caller's file and line as the cause.
+#define QF_PROFILED(ctx, st, name, launch)                  \
+    do {                                                    \
+        hipEvent_t _ev = qf::ctx_prof_begin((ctx), (st));   \
+        QF_CHECK_HIP(launch);                               \
+        qf::ctx_prof_end((ctx), (st), _ev, (name));         \
+    } while (0)
+// (a kernel launched in place: hipLaunchKernelGGL as an expression of its error)
+namespace qf {
+template <class... Params, class... Args>
+static inline hipError_t launch_kernel(void (*kern)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                                const Args&... args) {
+    hipLaunchKernelGGL(kern, grid, block, lds, st, static_cast<Params>(args)...);
+    return hipGetLastError();
+}
+}  // namespace qf

@@ -46,9 +46,8 @@
 #include "gf256_tables.h"
 #include "qf_fec.h"
 #include "qf_kernels.h"
+#include "qf_gf_dev.h"
 #include "qf_internal.h"
-
-#define QF_DEV __device__ __forceinline__
 
 namespace qf {
 
@@ -530,6 +529,24 @@ hipError_t launch_rank_update(const RankUpdateArgs& a, hipStream_t st) {
     }
 }
 
+hipError_t launch_rank(qf_ctx* ctx, const RowArrays& rows, uint32_t k, uint32_t r, uint32_t max_rows, uint32_t G,
+                       uint8_t* state, uint8_t* innovative, uint32_t* rank, int32_t* status, hipStream_t st) {
+    RankUpdateArgs fa{};
+    fa.row_index = rows.index;
+    fa.n_rows = rows.n_rows;
+    fa.row_coeffs = rows.coeffs;
+    fa.explog = ctx_explog(ctx);
+    fa.innovative = innovative;
+    fa.rank = rank;
+    fa.status = status;
+    fa.k = k;
+    fa.r = r;
+    fa.max_rows = max_rows;
+    fa.G = G;
+    fa.state = state;
+    return state ? launch_rank_update(fa, st) : launch_rank_filter(fa, st);
+}
+
 void RankBasis::reset(uint32_t k) {
     k_ = k;
     rank_ = 0;
@@ -579,35 +596,31 @@ extern "C" int qf_gf256_rank(uint32_t k, uint32_t n, const uint8_t* vectors, uin
     return QF_OK;
 }
 
-extern "C" int qf_rank_batch(qf_ctx* ctx, const qf_rank_shape* sh, uint32_t G, const uint16_t* row_index,
-                             const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* innovative,
-                             uint32_t* rank, int32_t* status) {
+// qf_rank_batch, and with `resume` qf_rank_update_batch from and into `state`.
+static int rank_run(qf_ctx* ctx, const qf_rank_shape* sh, uint32_t G, const uint16_t* row_index,
+                    const uint32_t* n_rows, const uint8_t* row_coeffs, bool resume, uint8_t* state,
+                    uint8_t* innovative, uint32_t* rank, int32_t* status) {
     if (!ctx || !sh) return QF_EINVAL;
     const uint32_t k = sh->k, r = sh->r, max_rows = sh->max_rows;
     if (k == 0 || k > 256 || max_rows == 0 || max_rows > 4096 || sh->flags != 0) return QF_EINVAL;
     if (!row_coeffs && r && (uint64_t)k + r > 256) return QF_ERANGE;
     if (G == 0) return QF_OK;
     if (!row_index || !rank || !status) return QF_EINVAL;
+    if (resume && (!state || !aligned16(state))) return QF_EINVAL;
     std::unique_lock<std::mutex> lk;
     int s = qf::ctx_lock(ctx, lk);
     if (s) return s;
     hipStream_t st = qf::ctx_stream(ctx);
-    qf::RankFilterArgs fa{};
-    fa.row_index = row_index;
-    fa.n_rows = n_rows;
-    fa.row_coeffs = row_coeffs;
-    fa.explog = qf::ctx_explog(ctx);
-    fa.innovative = innovative;
-    fa.rank = rank;
-    fa.status = status;
-    fa.k = k;
-    fa.r = r;
-    fa.max_rows = max_rows;
-    fa.G = G;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_rank_filter(fa, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_rank_filter");
+    const qf::RowArrays rows{nullptr, nullptr, row_index, n_rows, row_coeffs};
+    QF_PROFILED(ctx, st, resume ? "k_rank_update" : "k_rank_filter",
+                qf::launch_rank(ctx, rows, k, r, max_rows, G, state, innovative, rank, status, st));
     return QF_OK;
+}
+
+extern "C" int qf_rank_batch(qf_ctx* ctx, const qf_rank_shape* sh, uint32_t G, const uint16_t* row_index,
+                             const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* innovative,
+                             uint32_t* rank, int32_t* status) {
+    return rank_run(ctx, sh, G, row_index, n_rows, row_coeffs, false, nullptr, innovative, rank, status);
 }
 
 extern "C" size_t qf_rank_state_bytes(uint32_t k) { return qf::rank_state_bytes(k); }
@@ -615,32 +628,5 @@ extern "C" size_t qf_rank_state_bytes(uint32_t k) { return qf::rank_state_bytes(
 extern "C" int qf_rank_update_batch(qf_ctx* ctx, const qf_rank_shape* sh, uint32_t G, const uint16_t* row_index,
                                     const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* state,
                                     uint8_t* innovative, uint32_t* rank, int32_t* status) {
-    if (!ctx || !sh) return QF_EINVAL;
-    const uint32_t k = sh->k, r = sh->r, max_rows = sh->max_rows;
-    if (k == 0 || k > 256 || max_rows == 0 || max_rows > 4096 || sh->flags != 0) return QF_EINVAL;
-    if (!row_coeffs && r && (uint64_t)k + r > 256) return QF_ERANGE;
-    if (G == 0) return QF_OK;
-    if (!row_index || !state || !rank || !status) return QF_EINVAL;
-    if (reinterpret_cast<uintptr_t>(state) & 15) return QF_EINVAL;
-    std::unique_lock<std::mutex> lk;
-    int s = qf::ctx_lock(ctx, lk);
-    if (s) return s;
-    hipStream_t st = qf::ctx_stream(ctx);
-    qf::RankUpdateArgs fa{};
-    fa.row_index = row_index;
-    fa.n_rows = n_rows;
-    fa.row_coeffs = row_coeffs;
-    fa.explog = qf::ctx_explog(ctx);
-    fa.innovative = innovative;
-    fa.rank = rank;
-    fa.status = status;
-    fa.k = k;
-    fa.r = r;
-    fa.max_rows = max_rows;
-    fa.G = G;
-    fa.state = state;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_rank_update(fa, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_rank_update");
-    return QF_OK;
+    return rank_run(ctx, sh, G, row_index, n_rows, row_coeffs, true, state, innovative, rank, status);
 }

@@ -269,9 +269,6 @@ hipError_t launch_recode_prepare(const RecodePrepareArgs& a, hipStream_t st) {
 
 }  // namespace qf
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
 extern "C" int qf_recode_batch(qf_ctx* ctx, const qf_recode_shape* sh, uint32_t G, const uint8_t* rows,
                                const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
                                const uint8_t* mix, uint64_t seed, uint8_t* out, uint8_t* out_coeffs,
@@ -294,10 +291,12 @@ extern "C" int qf_recode_batch(qf_ctx* ctx, const qf_recode_shape* sh, uint32_t 
     // workspace: records [pass][G][(max_rows + 1) * 16] | n_out[G] | bound[G]
     const uint32_t passes = (m + 15) / 16;
     const uint64_t coef_gen_stride = ((uint64_t)max_rows + 1) * 16;
-    const size_t off_nout = round_up((size_t)passes * G * coef_gen_stride, 256);
-    const size_t off_bound = off_nout + round_up((size_t)G * 4, 256);
+    qf::WorkLayout wl;
+    const size_t off_coef = wl.take((size_t)passes * G * coef_gen_stride);
+    const size_t off_nout = wl.take((size_t)G * 4);
+    const size_t off_bound = wl.take((size_t)G * 4);
     uint8_t* w = nullptr;
-    s = qf::ctx_work(ctx, off_bound + (size_t)G * 4, &w);
+    s = qf::ctx_work(ctx, wl.size(), &w);
     if (s) return s;
     uint32_t* d_nout = reinterpret_cast<uint32_t*>(w + off_nout);
     uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
@@ -308,7 +307,7 @@ extern "C" int qf_recode_batch(qf_ctx* ctx, const qf_recode_shape* sh, uint32_t 
     pa.mix = mix;
     pa.explog = qf::ctx_explog(ctx);
     pa.seed = seed;
-    pa.coef_out = w;
+    pa.coef_out = w + off_coef;
     pa.coef_gen_stride = coef_gen_stride;
     pa.n_out = d_nout;
     pa.bound = d_bound;
@@ -320,9 +319,7 @@ extern "C" int qf_recode_batch(qf_ctx* ctx, const qf_recode_shape* sh, uint32_t 
     pa.max_rows = max_rows;
     pa.passes = passes;
     pa.G = G;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_recode_prepare(pa, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_recode_prepare");
+    QF_PROFILED(ctx, st, "k_recode_prepare", qf::launch_recode_prepare(pa, st));
     const uint32_t Lu = (L + 15) / 16;
     for (uint32_t p = 0; p < passes; ++p) {
         qf::CombineSlotsArgs a{};
@@ -332,7 +329,7 @@ extern "C" int qf_recode_batch(qf_ctx* ctx, const qf_recode_shape* sh, uint32_t 
         a.dst = out + (uint64_t)p * 16 * sh->out_row_stride;
         a.dst_gen_stride = sh->out_gen_stride;
         a.dst_row_stride = sh->out_row_stride;
-        a.coef = w + (uint64_t)p * G * coef_gen_stride;
+        a.coef = pa.coef_out + (uint64_t)p * G * coef_gen_stride;
         a.coef_gen_stride = coef_gen_stride;
         a.n_out = d_nout;
         a.bound = d_bound;
@@ -342,10 +339,8 @@ extern "C" int qf_recode_batch(qf_ctx* ctx, const qf_recode_shape* sh, uint32_t 
         a.Lu = Lu;
         a.zero_slot = max_rows;
         a.total_units = (uint64_t)G * Lu;
-        ev = qf::ctx_prof_begin(ctx, st);
-        std::string cname;
-        QF_CHECK_HIP(qf::ctx_combine_payload(ctx, a, st, &cname));
-        qf::ctx_prof_end(ctx, st, ev, cname);
+        std::string cname;   // the launch names the kernel it picked
+        QF_PROFILED(ctx, st, cname, qf::ctx_combine_payload(ctx, a, st, &cname));
     }
     return QF_OK;
 }

@@ -68,25 +68,6 @@ QF_DEV void wait_all(v2u& o, v4u& a, v4u& b, v4u& c, v4u& d) {
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(o), "+v"(a), "+v"(b), "+v"(c), "+v"(d)::"memory");
 }
 
-QF_DEV uint32_t low_bytes_mask(uint32_t nb) { return nb >= 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1; }
-
-// The unit at p of a row of len bytes, u16 = 16 * unit index: the bytes of the
-// unit at and after len are zero, and a unit without a valid byte is not loaded.
-QF_DEV uint4 load_row_unit(const uint8_t* p, uint32_t len, uint32_t u16) {
-    uint4 x = make_uint4(0, 0, 0, 0);
-    if (len > u16) {
-        x = *reinterpret_cast<const uint4*>(p);
-        const uint32_t v = len - u16;
-        if (v < 16) {
-            x.x &= low_bytes_mask(v);
-            x.y &= low_bytes_mask(v > 4 ? v - 4 : 0);
-            x.z &= low_bytes_mask(v > 8 ? v - 8 : 0);
-            x.w &= low_bytes_mask(v > 12 ? v - 12 : 0);
-        }
-    }
-    return x;
-}
-
 // One wave-item.  srcp: the lane's unit in its generation's source region at
 // offset 0 (region + 16u); gen_off: the generation's pair records from a.coef
 // (below 2^31, launch_combine_rows_at).  Pairs past the last one, (max_rows +
@@ -267,9 +248,6 @@ hipError_t launch_parse_frame_headers(const uint8_t* frames, uint64_t frame_stri
 
 }  // namespace qf
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
 extern "C" int qf_parse_frame_headers_dev(qf_ctx* ctx, uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows,
                                           const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
                                           const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
@@ -288,50 +266,107 @@ extern "C" int qf_parse_frame_headers_dev(qf_ctx* ctx, uint32_t k, uint32_t L, u
     int s = qf::ctx_lock(ctx, lk);
     if (s) return s;
     hipStream_t st = qf::ctx_stream(ctx);
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_parse_frame_headers(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
-                                                max_rows, row_index, n_rows, row_coeffs, row_len, row_off,
-                                                frame_status, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_parse_frame_headers");
+    QF_PROFILED(ctx, st, "k_parse_frame_headers",
+                qf::launch_parse_frame_headers(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
+                                               max_rows, row_index, n_rows, row_coeffs, row_len, row_off,
+                                               frame_status, st));
     return QF_OK;
 }
 
-// The arrays of k_sel_gather behind a dense call's workspace of `base` bytes:
-// one ctx_work allocation holds both (a second ctx_work call may move the first).
+// The arrays of k_sel_gather, taken behind a dense call's parts of the same
+// layout: one ctx_work allocation holds both (a second ctx_work call may move
+// the first).
 struct SelWork {
-    size_t off, len, index, n_rows, map, n_out, coeffs, end;
+    size_t off, len, index, n_rows, map, n_out, coeffs;
 };
-static SelWork sel_work(size_t base, uint32_t n_max, uint32_t max_rows, uint32_t k) {
+static SelWork sel_work(qf::WorkLayout& wl, uint32_t n_max, uint32_t max_rows, uint32_t k) {
     SelWork w;
     const size_t slots = (size_t)n_max * max_rows;
-    w.off = round_up(base, 256);
-    w.len = w.off + round_up(slots * 4, 256);
-    w.index = w.len + round_up(slots * 4, 256);
-    w.n_rows = w.index + round_up(slots * 2, 256);
-    w.map = w.n_rows + round_up((size_t)n_max * 4, 256);
-    w.n_out = w.map + round_up((size_t)n_max * 4, 256);
-    w.coeffs = w.n_out + round_up((size_t)n_max * 4, 256);
-    w.end = w.coeffs + slots * k;
+    w.off = wl.take(slots * 4);
+    w.len = wl.take(slots * 4);
+    w.index = wl.take(slots * 2);
+    w.n_rows = wl.take((size_t)n_max * 4);
+    w.map = wl.take((size_t)n_max * 4);
+    w.n_out = wl.take((size_t)n_max * 4);
+    w.coeffs = wl.take(slots * k);
     return w;
 }
 static bool sel_ok(const qf_gen_sel* sel) { return sel && sel->sel_dev && sel->n_max != 0 && sel->G_src != 0; }
 
+// k_sel_gather: the batch of sel->n_max generations the list stands for, in the
+// compact arrays at sw of the workspace w; *rows becomes those arrays and
+// *gen_map the source generation of each entry.  invalid_n_rows: the n_rows
+// that makes the call's control kernel answer an invalid entry with QF_EINVAL.
+// n_out_gen (nullable) receives n_out_listed for a listed entry and 0 for an
+// unused one.
+static int sel_gather(qf_ctx* ctx, hipStream_t st, const qf_gen_sel* sel, const SelWork& sw, uint8_t* w, uint32_t k,
+                      uint32_t max_rows, uint32_t invalid_n_rows, uint32_t n_out_listed, qf::RowArrays* rows,
+                      const uint32_t** gen_map, const uint32_t** n_out_gen) {
+    qf::SelGatherArgs ga{};
+    ga.sel = sel->sel_dev;
+    ga.n_sel = sel->n_sel_dev;
+    ga.row_off = rows->off;
+    ga.row_len = rows->len;
+    ga.row_index = rows->index;
+    ga.n_rows = rows->n_rows;
+    ga.row_coeffs = rows->coeffs;
+    ga.c_row_off = reinterpret_cast<uint32_t*>(w + sw.off);
+    ga.c_row_len = reinterpret_cast<uint32_t*>(w + sw.len);
+    ga.c_row_index = reinterpret_cast<uint16_t*>(w + sw.index);
+    ga.c_n_rows = reinterpret_cast<uint32_t*>(w + sw.n_rows);
+    ga.c_row_coeffs = w + sw.coeffs;
+    ga.gen_map = reinterpret_cast<uint32_t*>(w + sw.map);
+    if (n_out_gen) ga.n_out = reinterpret_cast<uint32_t*>(w + sw.n_out);
+    ga.n_max = sel->n_max;
+    ga.G_src = sel->G_src;
+    ga.k = k;
+    ga.max_rows = max_rows;
+    ga.invalid_n_rows = invalid_n_rows;
+    ga.n_out_listed = n_out_listed;
+    QF_PROFILED(ctx, st, "k_sel_gather", qf::launch_sel_gather(ga, st));
+    *rows = qf::RowArrays{ga.c_row_off, ga.c_row_len, ga.c_row_index, ga.c_n_rows, ga.c_row_coeffs};
+    *gen_map = ga.gen_map;
+    if (n_out_gen) *n_out_gen = ga.n_out;
+    return QF_OK;
+}
+
+// The payload passes of both calls: pass p writes output rows 16 p .. of every
+// generation from the pass's pair records, coef_gen_stride * G apart from a.coef.
+// a holds what the passes share; a.n_out_gen == nullptr: m rows per generation.
+static int rows_at_passes(qf_ctx* ctx, hipStream_t st, qf::CombineRowsAtArgs a, uint32_t passes, uint32_t G,
+                          uint32_t m, const uint32_t* gen_map) {
+    uint8_t* const dst = a.dst;
+    const uint8_t* const coef = a.coef;
+    a.tab256 = qf::ctx_tab256(ctx);
+    a.Lu = (a.L + 15) / 16;
+    a.total_units = (uint64_t)G * a.Lu;
+    for (uint32_t p = 0; p < passes; ++p) {
+        a.dst = dst + (uint64_t)p * 16 * a.dst_row_stride;
+        a.coef = coef + (uint64_t)p * G * a.coef_gen_stride;
+        a.n_out = 16;   // (with n_out_gen the per-generation count decides)
+        if (a.n_out_gen) a.pass = p;
+        else if (m - p * 16 < 16) a.n_out = m - p * 16;
+        QF_PROFILED(ctx, st, "k_combine_rows_at", qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st, gen_map));
+    }
+    return QF_OK;
+}
+
 // qf_recode_frames_dev (sel == nullptr), and qf_recode_frames_sel_dev over the
 // batch of G = sel->n_max generations that k_sel_gather makes of the list: the
 // same control kernel over the compact arrays, and the payload pass in its
-// per-generation-count form, so that an unused entry stores no row.
+// per-generation-count form (m for a listed entry, 0 for an unused one), so
+// that an unused entry stores no row.
 static int recode_frames_run(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint32_t G, const qf_gen_sel* sel,
-                             const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
-                             const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
-                             const uint8_t* mix, uint64_t seed, uint8_t* out, uint8_t* out_coeffs, uint32_t* out_len,
-                             int32_t* status) {
+                             const uint8_t* src, qf::RowArrays rows, const uint8_t* mix, uint64_t seed, uint8_t* out,
+                             uint8_t* out_coeffs, uint32_t* out_len, int32_t* status) {
     const uint32_t k = sh->k, L = sh->L, max_rows = sh->max_rows, m = sh->m;
     if (k == 0 || k > 255 || max_rows == 0 || max_rows > 255 || m == 0 || m > 64 || L == 0 || sh->flags != 0 ||
         sh->reserved != 0)
         return QF_EINVAL;
     if (sh->out_row_stride < L) return QF_EINVAL;
     if (G == 0) return QF_OK;
-    if (!src || !row_off || !row_len || !row_index || !row_coeffs || !out || !out_coeffs || !status) return QF_EINVAL;
+    if (!src || !rows.off || !rows.len || !rows.index || !rows.coeffs || !out || !out_coeffs || !status)
+        return QF_EINVAL;
     if (!aligned16(src) || (sh->src_gen_stride & 15) || !aligned16(out) || (sh->out_row_stride & 15) ||
         (sh->out_gen_stride & 15))
         return QF_EINVAL;
@@ -342,62 +377,31 @@ static int recode_frames_run(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint
     // workspace: pair records [pass][G][((max_rows + 1) / 2 + 1) * 48] | n_out[G] | bound[G] | min_len[G]
     const uint32_t passes = (m + 15) / 16;
     const uint64_t coef_gen_stride = ((uint64_t)(max_rows + 1) / 2 + 1) * qf::kPairRecBytes;
-    const size_t off_nout = round_up((size_t)passes * G * coef_gen_stride, 256);
-    const size_t off_bound = off_nout + round_up((size_t)G * 4, 256);
-    const size_t off_minlen = off_bound + round_up((size_t)G * 4, 256);
+    qf::WorkLayout wl;
+    const size_t off_coef = wl.take((size_t)passes * G * coef_gen_stride);
+    const size_t off_nout = wl.take((size_t)G * 4);
+    const size_t off_bound = wl.take((size_t)G * 4);
+    const size_t off_minlen = wl.take((size_t)G * 4);
+    const SelWork sw = sel ? sel_work(wl, G, max_rows, k) : SelWork{};
     uint8_t* w = nullptr;
-    const size_t dense_bytes = off_minlen + (size_t)G * 4;
-    const SelWork sw = sel ? sel_work(dense_bytes, G, max_rows, k) : SelWork{};
-    s = qf::ctx_work(ctx, sel ? sw.end : dense_bytes, &w);
+    s = qf::ctx_work(ctx, wl.size(), &w);
     if (s) return s;
-    uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
-    uint32_t* d_minlen = reinterpret_cast<uint32_t*>(w + off_minlen);
     const uint32_t* gen_map = nullptr;
     const uint32_t* n_out_gen = nullptr;
-    if (sel) {
-        qf::SelGatherArgs ga{};
-        ga.sel = sel->sel_dev;
-        ga.n_sel = sel->n_sel_dev;
-        ga.row_off = row_off;
-        ga.row_len = row_len;
-        ga.row_index = row_index;
-        ga.n_rows = n_rows;
-        ga.row_coeffs = row_coeffs;
-        ga.c_row_off = reinterpret_cast<uint32_t*>(w + sw.off);
-        ga.c_row_len = reinterpret_cast<uint32_t*>(w + sw.len);
-        ga.c_row_index = reinterpret_cast<uint16_t*>(w + sw.index);
-        ga.c_n_rows = reinterpret_cast<uint32_t*>(w + sw.n_rows);
-        ga.c_row_coeffs = w + sw.coeffs;
-        ga.gen_map = reinterpret_cast<uint32_t*>(w + sw.map);
-        ga.n_out = reinterpret_cast<uint32_t*>(w + sw.n_out);
-        ga.n_max = G;
-        ga.G_src = sel->G_src;
-        ga.k = k;
-        ga.max_rows = max_rows;
-        ga.invalid_n_rows = 0xFFFFFFFFu;   // n_rows > max_rows: k_recode_prepare's QF_EINVAL
-        ga.n_out_listed = m;
-        hipEvent_t evg = qf::ctx_prof_begin(ctx, st);
-        QF_CHECK_HIP(qf::launch_sel_gather(ga, st));
-        qf::ctx_prof_end(ctx, st, evg, "k_sel_gather");
-        row_off = ga.c_row_off;
-        row_len = ga.c_row_len;
-        row_index = ga.c_row_index;
-        n_rows = ga.c_n_rows;
-        row_coeffs = ga.c_row_coeffs;
-        gen_map = ga.gen_map;
-        n_out_gen = ga.n_out;
-    }
+    // (invalid entry: n_rows > max_rows, k_recode_prepare's QF_EINVAL)
+    if (sel && (s = sel_gather(ctx, st, sel, sw, w, k, max_rows, 0xFFFFFFFFu, m, &rows, &gen_map, &n_out_gen)))
+        return s;
     qf::RecodePrepareArgs pa{};
-    pa.row_index = row_index;
-    pa.n_rows = n_rows;
-    pa.row_coeffs = row_coeffs;
+    pa.row_index = rows.index;
+    pa.n_rows = rows.n_rows;
+    pa.row_coeffs = rows.coeffs;
     pa.mix = mix;
     pa.explog = qf::ctx_explog(ctx);
     pa.seed = seed;
-    pa.coef_out = w;
+    pa.coef_out = w + off_coef;
     pa.coef_gen_stride = coef_gen_stride;
     pa.n_out = reinterpret_cast<uint32_t*>(w + off_nout);
-    pa.bound = d_bound;
+    pa.bound = reinterpret_cast<uint32_t*>(w + off_bound);
     pa.out_coeffs = out_coeffs;
     pa.status = status;
     pa.k = k;
@@ -406,43 +410,27 @@ static int recode_frames_run(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint
     pa.max_rows = max_rows;
     pa.passes = passes;
     pa.G = G;
-    pa.row_off = row_off;
-    pa.row_len = row_len;
-    pa.min_len = d_minlen;
+    pa.row_off = rows.off;
+    pa.row_len = rows.len;
+    pa.min_len = reinterpret_cast<uint32_t*>(w + off_minlen);
     pa.out_len = out_len;
     pa.src_gen_stride = sh->src_gen_stride;
     pa.L = L;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_recode_prepare(pa, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_recode_prepare");
-    const uint32_t Lu = (L + 15) / 16;
-    for (uint32_t p = 0; p < passes; ++p) {
-        qf::CombineRowsAtArgs a{};
-        a.src = src;
-        a.src_gen_stride = sh->src_gen_stride;
-        a.dst = out + (uint64_t)p * 16 * sh->out_row_stride;
-        a.dst_gen_stride = sh->out_gen_stride;
-        a.dst_row_stride = sh->out_row_stride;
-        a.coef = w + (uint64_t)p * G * coef_gen_stride;
-        a.coef_gen_stride = coef_gen_stride;
-        a.bound = d_bound;
-        a.min_len = d_minlen;
-        a.tab256 = qf::ctx_tab256(ctx);
-        a.n_out = m - p * 16 < 16 ? m - p * 16 : 16;
-        a.L = L;
-        a.Lu = Lu;
-        a.max_rows = max_rows;
-        a.total_units = (uint64_t)G * Lu;
-        if (sel) {
-            a.n_out = 16;   // the per-generation count decides: m for a listed entry, 0 for an unused one
-            a.n_out_gen = n_out_gen;
-            a.pass = p;
-        }
-        ev = qf::ctx_prof_begin(ctx, st);
-        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st, gen_map));
-        qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");
-    }
-    return QF_OK;
+    QF_PROFILED(ctx, st, "k_recode_prepare", qf::launch_recode_prepare(pa, st));
+    qf::CombineRowsAtArgs a{};
+    a.src = src;
+    a.src_gen_stride = sh->src_gen_stride;
+    a.dst = out;
+    a.dst_gen_stride = sh->out_gen_stride;
+    a.dst_row_stride = sh->out_row_stride;
+    a.coef = pa.coef_out;
+    a.coef_gen_stride = coef_gen_stride;
+    a.bound = pa.bound;
+    a.min_len = pa.min_len;
+    a.L = L;
+    a.max_rows = max_rows;
+    a.n_out_gen = n_out_gen;
+    return rows_at_passes(ctx, st, a, passes, G, m, gen_map);
 }
 
 extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* sh, uint32_t G, const uint8_t* src,
@@ -451,8 +439,8 @@ extern "C" int qf_recode_frames_dev(qf_ctx* ctx, const qf_recode_frames_shape* s
                                     uint64_t seed, uint8_t* out, uint8_t* out_coeffs, uint32_t* out_len,
                                     int32_t* status) {
     if (!ctx || !sh) return QF_EINVAL;
-    return recode_frames_run(ctx, sh, G, nullptr, src, row_off, row_len, row_index, n_rows, row_coeffs, mix, seed, out,
-                             out_coeffs, out_len, status);
+    return recode_frames_run(ctx, sh, G, nullptr, src, {row_off, row_len, row_index, n_rows, row_coeffs}, mix, seed,
+                             out, out_coeffs, out_len, status);
 }
 
 extern "C" int qf_recode_frames_sel_dev(qf_ctx* ctx, const qf_recode_frames_shape* sh, const qf_gen_sel* sel,
@@ -461,8 +449,8 @@ extern "C" int qf_recode_frames_sel_dev(qf_ctx* ctx, const qf_recode_frames_shap
                                         const uint8_t* mix, uint64_t seed, uint8_t* out, uint8_t* out_coeffs,
                                         uint32_t* out_len, int32_t* status) {
     if (!ctx || !sh || !sel_ok(sel)) return QF_EINVAL;
-    return recode_frames_run(ctx, sh, sel->n_max, sel, src, row_off, row_len, row_index, n_rows, row_coeffs, mix, seed,
-                             out, out_coeffs, out_len, status);
+    return recode_frames_run(ctx, sh, sel->n_max, sel, src, {row_off, row_len, row_index, n_rows, row_coeffs}, mix,
+                             seed, out, out_coeffs, out_len, status);
 }
 
 // The receiver's step over the same row descriptions: k_rank_filter's flags as
@@ -472,10 +460,9 @@ extern "C" int qf_recode_frames_sel_dev(qf_ctx* ctx, const qf_recode_frames_shap
 // (sel as in recode_frames_run: the three control and payload kernels of the
 // dense call over the compact arrays, the payload pass reading through the map)
 static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const qf_gen_sel* sel,
-                             const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
-                             const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* rec,
-                             uint16_t* rec_index, uint32_t* n_rec, int32_t* status, uint32_t* rank,
-                             uint8_t* innovative, uint16_t* src_slot) {
+                             const uint8_t* src, qf::RowArrays rows, uint8_t* rec, uint16_t* rec_index,
+                             uint32_t* n_rec, int32_t* status, uint32_t* rank, uint8_t* innovative,
+                             uint16_t* src_slot) {
     qf::ctx_clear_payload_split(ctx);   // as qf_decode_innovative_batch: they apply to qf_decode_batch only
     const uint32_t k = sh->k, r = sh->r, L = sh->L, max_rows = sh->max_rows;
     if (k == 0 || k > 256 || max_rows == 0 || max_rows > 1024 || L == 0 || sh->flags != 0 || sh->reserved != 0)
@@ -483,13 +470,12 @@ static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint
     const uint32_t e_max = k < r ? k : r;
     if (e_max > 128 || sh->rec_row_stride < L) return QF_EINVAL;
     if (G == 0) return QF_OK;
-    if (!src || !row_off || !row_len || !row_index || !row_coeffs || !n_rec || !status) return QF_EINVAL;
+    if (!src || !rows.off || !rows.len || !rows.index || !rows.coeffs || !n_rec || !status) return QF_EINVAL;
     if (e_max && (!rec || !rec_index)) return QF_EINVAL;
     if (!aligned16(src) || (sh->src_gen_stride & 15) || !aligned16(rec) || (sh->rec_row_stride & 15) ||
         (sh->rec_gen_stride & 15))
         return QF_EINVAL;
-    const uint32_t e_lds = k < 128 ? k : 128;
-    if (qf::prepare_lds_bytes(k, e_lds, max_rows) > 160 * 1024) return QF_EINVAL;
+    if (qf::prepare_lds_bytes(k, k < 128 ? k : 128, max_rows) > 160 * 1024) return QF_EINVAL;
     std::unique_lock<std::mutex> lk;
     int s = qf::ctx_lock(ctx, lk);
     if (s) return s;
@@ -499,116 +485,53 @@ static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint
     const uint32_t passes = (e_max + 15) / 16;
     const uint32_t max_acc = k < max_rows ? k : max_rows;
     const uint64_t coef_gen_stride = ((uint64_t)(max_acc + 1) / 2 + 1) * qf::kPairRecBytes;
-    const size_t off_bound = round_up((size_t)(passes ? passes : 1) * G * coef_gen_stride, 256);
-    const size_t off_minlen = off_bound + round_up((size_t)G * 4, 256);
-    const size_t off_flags = off_minlen + round_up((size_t)G * 4, 256);
+    qf::WorkLayout wl;
+    const size_t off_coef = wl.take((size_t)(passes ? passes : 1) * G * coef_gen_stride);
+    const size_t off_bound = wl.take((size_t)G * 4);
+    const size_t off_minlen = wl.take((size_t)G * 4);
+    const size_t off_flags = wl.take(innovative ? 0 : (size_t)G * max_rows);
+    const SelWork sw = sel ? sel_work(wl, G, max_rows, k) : SelWork{};
     uint8_t* w = nullptr;
-    const size_t dense_bytes = innovative ? off_flags : off_flags + (size_t)G * max_rows;
-    const SelWork sw = sel ? sel_work(dense_bytes, G, max_rows, k) : SelWork{};
-    s = qf::ctx_work(ctx, sel ? sw.end : dense_bytes, &w);
+    s = qf::ctx_work(ctx, wl.size(), &w);
     if (s) return s;
-    uint32_t* d_bound = reinterpret_cast<uint32_t*>(w + off_bound);
-    uint32_t* d_minlen = reinterpret_cast<uint32_t*>(w + off_minlen);
     const uint32_t* gen_map = nullptr;
-    if (sel) {
-        qf::SelGatherArgs ga{};
-        ga.sel = sel->sel_dev;
-        ga.n_sel = sel->n_sel_dev;
-        ga.row_off = row_off;
-        ga.row_len = row_len;
-        ga.row_index = row_index;
-        ga.n_rows = n_rows;
-        ga.row_coeffs = row_coeffs;
-        ga.c_row_off = reinterpret_cast<uint32_t*>(w + sw.off);
-        ga.c_row_len = reinterpret_cast<uint32_t*>(w + sw.len);
-        ga.c_row_index = reinterpret_cast<uint16_t*>(w + sw.index);
-        ga.c_n_rows = reinterpret_cast<uint32_t*>(w + sw.n_rows);
-        ga.c_row_coeffs = w + sw.coeffs;
-        ga.gen_map = reinterpret_cast<uint32_t*>(w + sw.map);
-        ga.n_max = G;
-        ga.G_src = sel->G_src;
-        ga.k = k;
-        ga.max_rows = max_rows;
-        ga.invalid_n_rows = 1;   // one slot of index 0xFFFF: the control kernels' QF_EINVAL, rank 0
-        hipEvent_t evg = qf::ctx_prof_begin(ctx, st);
-        QF_CHECK_HIP(qf::launch_sel_gather(ga, st));
-        qf::ctx_prof_end(ctx, st, evg, "k_sel_gather");
-        row_off = ga.c_row_off;
-        row_len = ga.c_row_len;
-        row_index = ga.c_row_index;
-        n_rows = ga.c_n_rows;
-        row_coeffs = ga.c_row_coeffs;
-        gen_map = ga.gen_map;
-    }
-    qf::RankFilterArgs fa{};
-    fa.row_index = row_index;
-    fa.n_rows = n_rows;
-    fa.row_coeffs = row_coeffs;
-    fa.explog = qf::ctx_explog(ctx);
-    fa.innovative = innovative ? innovative : w + off_flags;
-    fa.rank = rank;
-    fa.status = nullptr;   // k_decode_prepare applies the same index rules and reports
-    fa.k = k;
-    fa.r = r;
-    fa.max_rows = max_rows;
-    fa.G = G;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_rank_filter(fa, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_rank_filter");
+    // (invalid entry: one slot of index 0xFFFF, the control kernels' QF_EINVAL, rank 0)
+    if (sel && (s = sel_gather(ctx, st, sel, sw, w, k, max_rows, 1, 0, &rows, &gen_map, nullptr))) return s;
+    uint8_t* flags = innovative ? innovative : w + off_flags;
+    // (no status from the filter: k_decode_prepare applies the same index rules and reports)
+    QF_PROFILED(ctx, st, "k_rank_filter",
+                qf::launch_rank(ctx, rows, k, r, max_rows, G, nullptr, flags, rank, nullptr, st));
     qf::PrepareArgs pa{};
-    pa.accept = fa.innovative;
-    pa.row_index = row_index;
-    pa.n_rows = n_rows;
-    pa.row_coeffs = row_coeffs;
-    pa.explog = qf::ctx_explog(ctx);
-    pa.coef_out = w;
+    qf::prepare_common(ctx, pa, rows, k, e_max, max_rows, G);
+    pa.accept = flags;
+    pa.coef_out = w + off_coef;
     pa.coef_gen_stride = coef_gen_stride;
     pa.n_out = n_rec;
-    pa.bound = d_bound;
+    pa.bound = reinterpret_cast<uint32_t*>(w + off_bound);
     pa.rec_index = rec_index;
     pa.status = status;
-    pa.k = k;
-    pa.e_max = e_max;
-    pa.e_lds = e_lds;
     pa.rep_limit = 256;
-    pa.max_rows = max_rows;
-    pa.max_rows_pad = (max_rows + 7) & ~7u;
-    pa.passes = passes;
-    pa.G = G;
-    pa.row_off = row_off;
-    pa.row_len = row_len;
-    pa.min_len = d_minlen;
+    pa.row_off = rows.off;
+    pa.row_len = rows.len;
+    pa.min_len = reinterpret_cast<uint32_t*>(w + off_minlen);
     pa.src_slot = src_slot;
     pa.src_gen_stride = sh->src_gen_stride;
     pa.L = L;
-    ev = qf::ctx_prof_begin(ctx, st);
-    QF_CHECK_HIP(qf::launch_decode_prepare(pa, st));
-    qf::ctx_prof_end(ctx, st, ev, "k_decode_prepare");
-    const uint32_t Lu = (L + 15) / 16;
-    for (uint32_t p = 0; p < passes; ++p) {
-        qf::CombineRowsAtArgs a{};
-        a.src = src;
-        a.src_gen_stride = sh->src_gen_stride;
-        a.dst = rec + (uint64_t)p * 16 * sh->rec_row_stride;
-        a.dst_gen_stride = sh->rec_gen_stride;
-        a.dst_row_stride = sh->rec_row_stride;
-        a.coef = w + (uint64_t)p * G * coef_gen_stride;
-        a.coef_gen_stride = coef_gen_stride;
-        a.bound = d_bound;
-        a.min_len = d_minlen;
-        a.tab256 = qf::ctx_tab256(ctx);
-        a.n_out = 16;
-        a.L = L;
-        a.Lu = Lu;
-        a.max_rows = max_acc;   // the records hold the accepted rows only
-        a.total_units = (uint64_t)G * Lu;
-        a.n_out_gen = n_rec;
-        a.pass = p;
-        ev = qf::ctx_prof_begin(ctx, st);
-        QF_CHECK_HIP(qf::launch_combine_rows_at(a, qf::ctx_num_cus(ctx), st, gen_map));
-        qf::ctx_prof_end(ctx, st, ev, "k_combine_rows_at");
-    }
-    return QF_OK;
+    QF_PROFILED(ctx, st, "k_decode_prepare", qf::launch_decode_prepare(pa, st));
+    qf::CombineRowsAtArgs a{};
+    a.src = src;
+    a.src_gen_stride = sh->src_gen_stride;
+    a.dst = rec;
+    a.dst_gen_stride = sh->rec_gen_stride;
+    a.dst_row_stride = sh->rec_row_stride;
+    a.coef = pa.coef_out;
+    a.coef_gen_stride = coef_gen_stride;
+    a.bound = pa.bound;
+    a.min_len = pa.min_len;
+    a.L = L;
+    a.max_rows = max_acc;   // the records hold the accepted rows only
+    a.n_out_gen = n_rec;
+    return rows_at_passes(ctx, st, a, passes, G, 0, gen_map);
 }
 
 extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const uint8_t* src,
@@ -617,8 +540,8 @@ extern "C" int qf_decode_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* s
                                     uint16_t* rec_index, uint32_t* n_rec, int32_t* status, uint32_t* rank,
                                     uint8_t* innovative, uint16_t* src_slot) {
     if (!ctx || !sh) return QF_EINVAL;
-    return decode_frames_run(ctx, sh, G, nullptr, src, row_off, row_len, row_index, n_rows, row_coeffs, rec, rec_index,
-                             n_rec, status, rank, innovative, src_slot);
+    return decode_frames_run(ctx, sh, G, nullptr, src, {row_off, row_len, row_index, n_rows, row_coeffs}, rec,
+                             rec_index, n_rec, status, rank, innovative, src_slot);
 }
 
 extern "C" int qf_decode_frames_sel_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, const qf_gen_sel* sel,
@@ -627,6 +550,6 @@ extern "C" int qf_decode_frames_sel_dev(qf_ctx* ctx, const qf_decode_frames_shap
                                         uint8_t* rec, uint16_t* rec_index, uint32_t* n_rec, int32_t* status,
                                         uint32_t* rank, uint8_t* innovative, uint16_t* src_slot) {
     if (!ctx || !sh || !sel_ok(sel)) return QF_EINVAL;
-    return decode_frames_run(ctx, sh, sel->n_max, sel, src, row_off, row_len, row_index, n_rows, row_coeffs, rec,
+    return decode_frames_run(ctx, sh, sel->n_max, sel, src, {row_off, row_len, row_index, n_rows, row_coeffs}, rec,
                              rec_index, n_rec, status, rank, innovative, src_slot);
 }

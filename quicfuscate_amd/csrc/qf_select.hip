@@ -24,9 +24,8 @@
 
 #include "qf_fec.h"
 #include "qf_kernels.h"
+#include "qf_gf_dev.h"
 #include "qf_internal.h"
-
-#define QF_DEV __device__ __forceinline__
 
 namespace qf {
 
@@ -217,6 +216,15 @@ __global__ void __launch_bounds__(256) k_stream_reset(StreamResetArgs a) {
 
 }  // namespace
 
+// Both kernels of qf_gen_select_dev, in stream order.
+static hipError_t launch_gen_select(const GenSelectArgs& a, uint32_t blocks, hipStream_t st) {
+    hipLaunchKernelGGL(k_gen_select_count, dim3(blocks), dim3(kSelThreads), 0, st, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_gen_select_scatter, dim3(blocks), dim3(kSelThreads), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_sel_gather(const SelGatherArgs& a, hipStream_t st) {
     if (a.n_max == 0) return hipSuccess;
     if (!a.sel || a.k == 0 || a.k > 256 || a.max_rows == 0 || a.max_rows > 1024 || a.G_src == 0)
@@ -258,12 +266,7 @@ extern "C" int qf_gen_select_dev(qf_ctx* ctx, uint32_t G, const uint32_t* rank, 
     a.min_rank = min_rank;
     a.n_max = n_max;
     a.mark = flags & QF_SELECT_MARK;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    hipLaunchKernelGGL(qf::k_gen_select_count, dim3(blocks), dim3(qf::kSelThreads), 0, st, a);
-    QF_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(qf::k_gen_select_scatter, dim3(blocks), dim3(qf::kSelThreads), 0, st, a);
-    QF_CHECK_HIP(hipGetLastError());
-    qf::ctx_prof_end(ctx, st, ev, "k_gen_select");
+    QF_PROFILED(ctx, st, "k_gen_select", qf::launch_gen_select(a, blocks, st));
     return QF_OK;
 }
 
@@ -290,9 +293,7 @@ extern "C" int qf_stream_reset_dev(qf_ctx* ctx, uint32_t k, const qf_gen_sel* se
     // a lane per unit; the grid is bounded and strides over the rest
     const uint64_t need = (a.total + 255) / 256;
     const uint64_t most = (uint64_t)(qf::ctx_num_cus(ctx) > 0 ? qf::ctx_num_cus(ctx) : 1) * 64;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    hipLaunchKernelGGL(qf::k_stream_reset, dim3((uint32_t)(need < most ? need : most)), dim3(256), 0, st, a);
-    QF_CHECK_HIP(hipGetLastError());
-    qf::ctx_prof_end(ctx, st, ev, "k_stream_reset");
+    const dim3 grid((uint32_t)(need < most ? need : most));
+    QF_PROFILED(ctx, st, "k_stream_reset", qf::launch_kernel(qf::k_stream_reset, grid, dim3(256), 0, st, a));
     return QF_OK;
 }

@@ -23,9 +23,8 @@
 #include <mutex>
 
 #include "qf_fec.h"
+#include "qf_gf_dev.h"
 #include "qf_internal.h"
-
-#define QF_DEV __device__ __forceinline__
 
 namespace qf {
 
@@ -130,8 +129,6 @@ __global__ void __launch_bounds__(64) k_store_prepare(StorePrepareArgs a) {
     }
 }
 
-QF_DEV uint32_t low_bytes(uint32_t nb) { return nb >= 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1; }
-
 __global__ void __launch_bounds__(256) k_store_rows(StoreRowsArgs a) {
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < a.total; f += step) {
@@ -143,14 +140,7 @@ __global__ void __launch_bounds__(256) k_store_rows(StoreRowsArgs a) {
         if (j >= gn.y) continue;
         const uint2 r = a.rec[row];      // {row_off, row_len}
         if (r.y <= u16) continue;        // no byte of the row in this unit
-        uint4 x = *reinterpret_cast<const uint4*>(a.src + g * a.src_gen_stride + r.x + u16);
-        const uint32_t v = r.y - u16;
-        if (v < 16) {
-            x.x &= low_bytes(v);
-            x.y &= low_bytes(v > 4 ? v - 4 : 0);
-            x.z &= low_bytes(v > 8 ? v - 8 : 0);
-            x.w &= low_bytes(v > 12 ? v - 12 : 0);
-        }
+        const uint4 x = load_row_unit(a.src + g * a.src_gen_stride + r.x + u16, r.y, u16);
         *reinterpret_cast<uint4*>(a.store + g * a.store_gen_stride + (uint64_t)(gn.x + j) * a.store_row_stride + u16) = x;
     }
 }
@@ -158,9 +148,6 @@ __global__ void __launch_bounds__(256) k_store_rows(StoreRowsArgs a) {
 }  // namespace
 
 }  // namespace qf
-
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
 extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32_t G, const uint8_t* src,
                                    const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
@@ -188,9 +175,11 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     if (s) return s;
     hipStream_t st = qf::ctx_stream(ctx);
     // workspace: records [G][max_rows] {offset, length} | [G] {first store slot, count}
-    const size_t off_gen = round_up((size_t)G * max_rows * sizeof(uint2), 256);
+    qf::WorkLayout wl;
+    const size_t off_rec = wl.take((size_t)G * max_rows * sizeof(uint2));
+    const size_t off_gen = wl.take((size_t)G * sizeof(uint2));
     uint8_t* w = nullptr;
-    s = qf::ctx_work(ctx, off_gen + (size_t)G * sizeof(uint2), &w);
+    s = qf::ctx_work(ctx, wl.size(), &w);
     if (s) return s;
     qf::StorePrepareArgs pa{};
     pa.row_off = row_off;
@@ -205,7 +194,7 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     pa.store_coeffs = store_coeffs;
     pa.store_n = store_n;
     pa.status = status;
-    pa.rec = reinterpret_cast<uint2*>(w);
+    pa.rec = reinterpret_cast<uint2*>(w + off_rec);
     pa.gen = reinterpret_cast<uint2*>(w + off_gen);
     pa.src_gen_stride = sh->src_gen_stride;
     pa.store_row_stride = sh->store_row_stride;
@@ -213,10 +202,8 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     pa.L = L;
     pa.max_rows = max_rows;
     pa.cap = cap;
-    hipEvent_t ev = qf::ctx_prof_begin(ctx, st);
-    hipLaunchKernelGGL(qf::k_store_prepare, dim3(G), dim3(64), 0, st, pa);
-    QF_CHECK_HIP(hipGetLastError());
-    qf::ctx_prof_end(ctx, st, ev, "k_store_prepare");
+    QF_PROFILED(ctx, st, "k_store_prepare",
+                qf::launch_kernel(qf::k_store_prepare, dim3(G), dim3(64), 0, st, pa));
     qf::StoreRowsArgs ra{};
     ra.src = src;
     ra.store = store;
@@ -231,9 +218,7 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     // a lane per unit; the grid is bounded and strides over the rest
     const uint64_t need = (ra.total + 255) / 256;
     const uint64_t most = (uint64_t)(qf::ctx_num_cus(ctx) > 0 ? qf::ctx_num_cus(ctx) : 1) * 64;
-    ev = qf::ctx_prof_begin(ctx, st);
-    hipLaunchKernelGGL(qf::k_store_rows, dim3((uint32_t)(need < most ? need : most)), dim3(256), 0, st, ra);
-    QF_CHECK_HIP(hipGetLastError());
-    qf::ctx_prof_end(ctx, st, ev, "k_store_rows");
+    const dim3 grid((uint32_t)(need < most ? need : most));
+    QF_PROFILED(ctx, st, "k_store_rows", qf::launch_kernel(qf::k_store_rows, grid, dim3(256), 0, st, ra));
     return QF_OK;
 }

@@ -18,10 +18,9 @@
 #include <stdint.h>
 
 #include "qf_fec.h"
+#include "qf_gf_dev.h"
 
 namespace {
-
-#define QF_DEV __device__ __forceinline__
 
 // bytes [off, off + 4) of a buffer read through aligned dwords
 QF_DEV uint32_t load_u32_unaligned(const uint8_t* base, uint64_t off) {

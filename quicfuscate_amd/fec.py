@@ -232,6 +232,21 @@ def _need(t, nbytes: int, what: str) -> None:
         raise ValueError(f"{what}: {have} bytes, the call needs {nbytes}")
 
 
+def _opt(t) -> Optional[int]:
+    """The device pointer of an optional tensor (None: NULL)."""
+    return _ptr(t) if t is not None else None
+
+
+def _need_rows(G: int, max_rows: int, k: int, row_off, row_len, row_index, row_coeffs, n_rows) -> None:
+    """_need for the arrays that describe the max_rows slots of each of G
+    generations (each where it is given)."""
+    _need(row_off, 4 * G * max_rows, "row_off")
+    _need(row_len, 4 * G * max_rows, "row_len")
+    _need(row_index, 2 * G * max_rows, "row_index")
+    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need(n_rows, 4 * G, "n_rows")
+
+
 def _span(G: int, gen_stride: int, rows: int, row_stride: int, L: int) -> int:
     """Bytes from the first byte of generation 0 to the end of the last row."""
     return 0 if G == 0 or rows == 0 else (G - 1) * gen_stride + (rows - 1) * row_stride + L
@@ -413,22 +428,17 @@ def rank_batch(row_index, rank, status, k: int, *, r: int = 0, max_rows: int, G:
     optionally, which slots are innovative (innovative: [G, max_rows] bytes,
     1 iff the slot's vector is not in the span of the slots before it).
     Indices, n_rows and row_coeffs as decode_batch; no payload is read."""
-    _need(row_index, 2 * G * max_rows, "row_index")
+    _need_rows(G, max_rows, k, None, None, row_index, row_coeffs, n_rows)
     _need(rank, 4 * G, "rank")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if row_coeffs is not None:
-        _need(row_coeffs, G * max_rows * k, "row_coeffs")
-    if innovative is not None:
-        _need(innovative, G * max_rows, "innovative")
+    _need(innovative, G * max_rows, "innovative")
     ctx = ctx or default_context()
     sh = L.RankShape(k, r, max_rows, 0)
     check(L._lib().qf_rank_batch(
         ctx.handle, ctypes.byref(sh), G, _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None,
-        _ptr(row_coeffs) if row_coeffs is not None else None,
-        _ptr(innovative) if innovative is not None else None,
+        _opt(n_rows),
+        _opt(row_coeffs),
+        _opt(innovative),
         _ptr(rank), _ptr(status)), "rank_batch")
 
 
@@ -442,29 +452,23 @@ def decode_innovative_batch(rows, row_index, rec, rec_index, n_rec, status, k: i
     innovative ([G, max_rows] bytes) are optional outputs, as rank_batch's."""
     em = min(k, r)
     _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
-    _need(row_index, 2 * G * max_rows, "row_index")
+    _need_rows(G, max_rows, k, None, None, row_index, row_coeffs, n_rows)
     _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, Lb), "rec")
     _need(rec_index, 2 * G * em, "rec_index (min(k, r) entries per generation)")
     _need(n_rec, 4 * G, "n_rec")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if row_coeffs is not None:
-        _need(row_coeffs, G * max_rows * k, "row_coeffs")
-    if rank is not None:
-        _need(rank, 4 * G, "rank")
-    if innovative is not None:
-        _need(innovative, G * max_rows, "innovative")
+    _need(rank, 4 * G, "rank")
+    _need(innovative, G * max_rows, "innovative")
     ctx = ctx or default_context()
     sh = L.DecodeShape(k, r, Lb, max_rows, row_stride, rows_gen_stride, rec_row_stride, rec_gen_stride)
     check(L._lib().qf_decode_innovative_batch(
         ctx.handle, ctypes.byref(sh), G, _ptr(rows), _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None,
-        _ptr(row_coeffs) if row_coeffs is not None else None,
-        _ptr(rec) if rec is not None else None, _ptr(rec_index) if rec_index is not None else None,
+        _opt(n_rows),
+        _opt(row_coeffs),
+        _opt(rec), _opt(rec_index),
         _ptr(n_rec), _ptr(status),
-        _ptr(rank) if rank is not None else None,
-        _ptr(innovative) if innovative is not None else None), "decode_innovative_batch")
+        _opt(rank),
+        _opt(innovative)), "decode_innovative_batch")
 
 
 def frame_payload_offset(k: int) -> int:
@@ -489,27 +493,19 @@ def frame_rows(rows, frames, frame_len, k: int, Lb: int, *, r: int = 0, max_rows
         _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
     _need(frames, _span(G * max_rows, frame_stride, 1, 0, P + Lb), "frames")
     _need(frame_len, 4 * G * max_rows, "frame_len")
-    if frame_off is not None:
-        _need(frame_off, 4 * G * max_rows, "frame_off")
-    if row_index is not None:
-        _need(row_index, 2 * G * max_rows, "row_index")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if row_coeffs is not None:
-        _need(row_coeffs, G * max_rows * k, "row_coeffs")
-    if row_len is not None:
-        _need(row_len, 4 * G * max_rows, "row_len")
+    _need(frame_off, 4 * G * max_rows, "frame_off")
+    _need_rows(G, max_rows, k, None, row_len, row_index, row_coeffs, n_rows)
     ctx = ctx or default_context()
     sh = L.FrameRowsShape(k, r, Lb, max_rows, L.QF_FRAME_IN_PLACE if in_place else 0, 0, row_stride, rows_gen_stride,
                           frame_stride)
     check(L._lib().qf_frame_rows_dev(
         ctx.handle, ctypes.byref(sh), G, _ptr(rows) if (rows is not None and not in_place) else None,
-        _ptr(row_index) if row_index is not None else None,
-        _ptr(n_rows) if n_rows is not None else None,
-        _ptr(row_coeffs) if row_coeffs is not None else None,
-        _ptr(row_len) if row_len is not None else None,
+        _opt(row_index),
+        _opt(n_rows),
+        _opt(row_coeffs),
+        _opt(row_len),
         _ptr(frames), _ptr(frame_len),
-        _ptr(frame_off) if frame_off is not None else None), "frame_rows")
+        _opt(frame_off)), "frame_rows")
 
 
 def parse_frames_coded(frames, frame_len, ids, rows, row_index, n_rows, frame_status, row_coeffs, k: int, Lb: int, *,
@@ -525,23 +521,17 @@ def parse_frames_coded(frames, frame_len, ids, rows, row_index, n_rows, frame_st
     _need(frame_len, 4 * G * max_rows, "frame_len")
     _need(ids, 8 * G * max_rows, "ids")
     _need(rows, _span(G, rows_gen_stride, max_rows, row_stride, Lb), "rows")
-    _need(row_index, 2 * G * max_rows, "row_index")
-    _need(n_rows, 4 * G, "n_rows")
+    _need_rows(G, max_rows, k, None, row_len, row_index, row_coeffs, n_rows)
     _need(frame_status, 4 * G * max_rows, "frame_status")
-    _need(row_coeffs, G * max_rows * k, "row_coeffs")
-    if n_frames is not None:
-        _need(n_frames, 4 * G, "n_frames")
-    if frame_off is not None:
-        _need(frame_off, 4 * G * max_rows, "frame_off")
-    if row_len is not None:
-        _need(row_len, 4 * G * max_rows, "row_len")
+    _need(n_frames, 4 * G, "n_frames")
+    _need(frame_off, 4 * G * max_rows, "frame_off")
     ctx = ctx or default_context()
     check(L._lib().qf_parse_frames_coded_dev(
         ctx.handle, k, Lb, G, max_rows, _ptr(frames), frame_stride, _ptr(frame_len),
-        _ptr(frame_off) if frame_off is not None else None, _ptr(ids),
-        _ptr(n_frames) if n_frames is not None else None,
+        _opt(frame_off), _ptr(ids),
+        _opt(n_frames),
         _ptr(rows), row_stride, rows_gen_stride, _ptr(row_index), _ptr(n_rows), _ptr(row_coeffs),
-        _ptr(row_len) if row_len is not None else None, _ptr(frame_status)), "parse_frames_coded")
+        _opt(row_len), _ptr(frame_status)), "parse_frames_coded")
 
 
 def parse_frame_headers(frames, frame_len, ids, row_index, n_rows, frame_status, row_coeffs, row_len, row_off,
@@ -556,21 +546,15 @@ def parse_frame_headers(frames, frame_len, ids, row_index, n_rows, frame_status,
     _need(frames, G * max_rows * frame_stride, "frames")
     _need(frame_len, 4 * G * max_rows, "frame_len")
     _need(ids, 8 * G * max_rows, "ids")
-    _need(row_index, 2 * G * max_rows, "row_index")
-    _need(n_rows, 4 * G, "n_rows")
+    _need_rows(G, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
     _need(frame_status, 4 * G * max_rows, "frame_status")
-    _need(row_coeffs, G * max_rows * k, "row_coeffs")
-    _need(row_len, 4 * G * max_rows, "row_len")
-    _need(row_off, 4 * G * max_rows, "row_off")
-    if n_frames is not None:
-        _need(n_frames, 4 * G, "n_frames")
-    if frame_off is not None:
-        _need(frame_off, 4 * G * max_rows, "frame_off")
+    _need(n_frames, 4 * G, "n_frames")
+    _need(frame_off, 4 * G * max_rows, "frame_off")
     ctx = ctx or default_context()
     check(L._lib().qf_parse_frame_headers_dev(
         ctx.handle, k, Lb, G, max_rows, _ptr(frames), frame_stride, _ptr(frame_len),
-        _ptr(frame_off) if frame_off is not None else None, _ptr(ids),
-        _ptr(n_frames) if n_frames is not None else None,
+        _opt(frame_off), _ptr(ids),
+        _opt(n_frames),
         _ptr(row_index), _ptr(n_rows), _ptr(row_coeffs), _ptr(row_len), _ptr(row_off), _ptr(frame_status)),
         "parse_frame_headers")
 
@@ -585,26 +569,19 @@ def recode_frames(src, row_off, row_len, row_index, row_coeffs, out, out_coeffs,
     max_rows * frame_stride).  out_len: optional [G, m] u32, the longest row
     length of each generation (frame_rows' row_len for the recoded rows)."""
     _need(src, G * src_gen_stride, "src")
-    _need(row_off, 4 * G * max_rows, "row_off")
-    _need(row_len, 4 * G * max_rows, "row_len")
-    _need(row_index, 2 * G * max_rows, "row_index")
-    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need_rows(G, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
     _need(out, _span(G, out_gen_stride, m, out_row_stride, Lb), "out")
     _need(out_coeffs, G * m * k, "out_coeffs (m vectors of k bytes per generation)")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if mix is not None:
-        _need(mix, G * m * max_rows, "mix")
-    if out_len is not None:
-        _need(out_len, 4 * G * m, "out_len")
+    _need(mix, G * m * max_rows, "mix")
+    _need(out_len, 4 * G * m, "out_len")
     ctx = ctx or default_context()
     sh = L.RecodeFramesShape(k, Lb, max_rows, m, 0, 0, src_gen_stride, out_row_stride, out_gen_stride)
     check(L._lib().qf_recode_frames_dev(
         ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
-        _ptr(mix) if mix is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
-        _ptr(out), _ptr(out_coeffs), _ptr(out_len) if out_len is not None else None, _ptr(status)),
+        _opt(n_rows), _ptr(row_coeffs),
+        _opt(mix), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _ptr(out), _ptr(out_coeffs), _opt(out_len), _ptr(status)),
         "recode_frames")
 
 
@@ -620,32 +597,24 @@ def decode_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, 
     for a recovered one (found in rec through rec_index)."""
     em = min(k, r)
     _need(src, G * src_gen_stride, "src")
-    _need(row_off, 4 * G * max_rows, "row_off")
-    _need(row_len, 4 * G * max_rows, "row_len")
-    _need(row_index, 2 * G * max_rows, "row_index")
-    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need_rows(G, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
     _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, Lb), "rec")
     _need(rec_index, 2 * G * em, "rec_index (min(k, r) entries per generation)")
     _need(n_rec, 4 * G, "n_rec")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if rank is not None:
-        _need(rank, 4 * G, "rank")
-    if innovative is not None:
-        _need(innovative, G * max_rows, "innovative")
-    if src_slot is not None:
-        _need(src_slot, 2 * G * k, "src_slot")
+    _need(rank, 4 * G, "rank")
+    _need(innovative, G * max_rows, "innovative")
+    _need(src_slot, 2 * G * k, "src_slot")
     ctx = ctx or default_context()
     sh = L.DecodeFramesShape(k, r, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride)
     check(L._lib().qf_decode_frames_dev(
         ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
-        _ptr(rec) if rec is not None else None, _ptr(rec_index) if rec_index is not None else None,
+        _opt(n_rows), _ptr(row_coeffs),
+        _opt(rec), _opt(rec_index),
         _ptr(n_rec), _ptr(status),
-        _ptr(rank) if rank is not None else None,
-        _ptr(innovative) if innovative is not None else None,
-        _ptr(src_slot) if src_slot is not None else None), "decode_frames")
+        _opt(rank),
+        _opt(innovative),
+        _opt(src_slot)), "decode_frames")
 
 
 def rank_state_bytes(k: int) -> int:
@@ -661,24 +630,19 @@ def rank_update_batch(row_index, state, rank, status, k: int, *, r: int = 0, max
     aligned, all zero = nothing received).  The flags of successive calls,
     concatenated, and the last rank are those of one rank_batch over all the
     slots.  A generation without a slot in the call is not written."""
-    _need(row_index, 2 * G * max_rows, "row_index")
+    _need_rows(G, max_rows, k, None, None, row_index, row_coeffs, n_rows)
     _need(state, G * rank_state_bytes(k), "state (rank_state_bytes(k) per generation)")
     _need(rank, 4 * G, "rank")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if row_coeffs is not None:
-        _need(row_coeffs, G * max_rows * k, "row_coeffs")
-    if innovative is not None:
-        _need(innovative, G * max_rows, "innovative")
+    _need(innovative, G * max_rows, "innovative")
     ctx = ctx or default_context()
     sh = L.RankShape(k, r, max_rows, 0)
     check(L._lib().qf_rank_update_batch(
         ctx.handle, ctypes.byref(sh), G, _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None,
-        _ptr(row_coeffs) if row_coeffs is not None else None,
+        _opt(n_rows),
+        _opt(row_coeffs),
         _ptr(state),
-        _ptr(innovative) if innovative is not None else None,
+        _opt(innovative),
         _ptr(rank), _ptr(status)), "rank_update_batch")
 
 
@@ -692,10 +656,7 @@ def store_append(src, row_off, row_len, row_index, row_coeffs, store, store_off,
     store arrays with max_rows = cap and src_gen_stride = store_gen_stride are
     the inputs of decode_frames and (cap <= 255) recode_frames."""
     _need(src, G * src_gen_stride, "src")
-    _need(row_off, 4 * G * max_rows, "row_off")
-    _need(row_len, 4 * G * max_rows, "row_len")
-    _need(row_index, 2 * G * max_rows, "row_index")
-    _need(row_coeffs, G * max_rows * k, "row_coeffs")
+    _need_rows(G, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
     _need(store, _span(G, store_gen_stride, cap, store_row_stride, (Lb + 15) // 16 * 16), "store")
     _need(store_off, 4 * G * cap, "store_off")
     _need(store_len, 4 * G * cap, "store_len")
@@ -703,16 +664,13 @@ def store_append(src, row_off, row_len, row_index, row_coeffs, store, store_off,
     _need(store_coeffs, G * cap * k, "store_coeffs")
     _need(store_n, 4 * G, "store_n")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G, "n_rows")
-    if take is not None:
-        _need(take, G * max_rows, "take")
+    _need(take, G * max_rows, "take")
     ctx = ctx or default_context()
     sh = L.StoreShape(k, Lb, max_rows, cap, 0, 0, src_gen_stride, store_row_stride, store_gen_stride)
     check(L._lib().qf_store_append_dev(
         ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
-        _ptr(take) if take is not None else None,
+        _opt(n_rows), _ptr(row_coeffs),
+        _opt(take),
         _ptr(store), _ptr(store_off), _ptr(store_len), _ptr(store_index), _ptr(store_coeffs), _ptr(store_n),
         _ptr(status)), "store_append")
 
@@ -730,22 +688,19 @@ def gen_select(rank, sel, n_sel, *, G: int, min_rank: int, n_max: int, seen=None
     _need(n_sel, 4, "n_sel")
     if G:
         _need(rank, 4 * G, "rank")
-    if seen is not None:
-        _need(seen, 4 * G, "seen")
-    if n_match is not None:
-        _need(n_match, 4, "n_match")
+    _need(seen, 4 * G, "seen")
+    _need(n_match, 4, "n_match")
     ctx = ctx or default_context()
     check(L._lib().qf_gen_select_dev(
-        ctx.handle, G, _ptr(rank) if rank is not None else None, _ptr(seen) if seen is not None else None,
+        ctx.handle, G, _opt(rank), _opt(seen),
         min_rank, QF_SELECT_MARK if mark else 0, n_max, _ptr(sel), _ptr(n_sel),
-        _ptr(n_match) if n_match is not None else None), "gen_select")
+        _opt(n_match)), "gen_select")
 
 
 def _gen_sel(sel, n_sel, n_max: int, G_src: int) -> "L.GenSel":
     _need(sel, 4 * n_max, "sel")
-    if n_sel is not None:
-        _need(n_sel, 4, "n_sel")
-    return L.GenSel(_ptr(sel), _ptr(n_sel) if n_sel is not None else None, n_max, G_src)
+    _need(n_sel, 4, "n_sel")
+    return L.GenSel(_ptr(sel), _opt(n_sel), n_max, G_src)
 
 
 def decode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status,
@@ -759,33 +714,25 @@ def decode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, 
     em = min(k, r)
     G = n_max
     _need(src, G_src * src_gen_stride, "src")
-    _need(row_off, 4 * G_src * max_rows, "row_off")
-    _need(row_len, 4 * G_src * max_rows, "row_len")
-    _need(row_index, 2 * G_src * max_rows, "row_index")
-    _need(row_coeffs, G_src * max_rows * k, "row_coeffs")
+    _need_rows(G_src, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
     _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, Lb), "rec")
     _need(rec_index, 2 * G * em, "rec_index (min(k, r) entries per list entry)")
     _need(n_rec, 4 * G, "n_rec")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G_src, "n_rows")
-    if rank is not None:
-        _need(rank, 4 * G, "rank")
-    if innovative is not None:
-        _need(innovative, G * max_rows, "innovative")
-    if src_slot is not None:
-        _need(src_slot, 2 * G * k, "src_slot")
+    _need(rank, 4 * G, "rank")
+    _need(innovative, G * max_rows, "innovative")
+    _need(src_slot, 2 * G * k, "src_slot")
     gs = _gen_sel(sel, n_sel, n_max, G_src)
     ctx = ctx or default_context()
     sh = L.DecodeFramesShape(k, r, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride)
     check(L._lib().qf_decode_frames_sel_dev(
         ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
-        _ptr(rec) if rec is not None else None, _ptr(rec_index) if rec_index is not None else None,
+        _opt(n_rows), _ptr(row_coeffs),
+        _opt(rec), _opt(rec_index),
         _ptr(n_rec), _ptr(status),
-        _ptr(rank) if rank is not None else None,
-        _ptr(innovative) if innovative is not None else None,
-        _ptr(src_slot) if src_slot is not None else None), "decode_frames_sel")
+        _opt(rank),
+        _opt(innovative),
+        _opt(src_slot)), "decode_frames_sel")
 
 
 def recode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, out, out_coeffs, status, k: int,
@@ -799,27 +746,20 @@ def recode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, 
     written."""
     G = n_max
     _need(src, G_src * src_gen_stride, "src")
-    _need(row_off, 4 * G_src * max_rows, "row_off")
-    _need(row_len, 4 * G_src * max_rows, "row_len")
-    _need(row_index, 2 * G_src * max_rows, "row_index")
-    _need(row_coeffs, G_src * max_rows * k, "row_coeffs")
+    _need_rows(G_src, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
     _need(out, _span(G, out_gen_stride, m, out_row_stride, Lb), "out")
     _need(out_coeffs, G * m * k, "out_coeffs (m vectors of k bytes per list entry)")
     _need(status, 4 * G, "status")
-    if n_rows is not None:
-        _need(n_rows, 4 * G_src, "n_rows")
-    if mix is not None:
-        _need(mix, G * m * max_rows, "mix")
-    if out_len is not None:
-        _need(out_len, 4 * G * m, "out_len")
+    _need(mix, G * m * max_rows, "mix")
+    _need(out_len, 4 * G * m, "out_len")
     gs = _gen_sel(sel, n_sel, n_max, G_src)
     ctx = ctx or default_context()
     sh = L.RecodeFramesShape(k, Lb, max_rows, m, 0, 0, src_gen_stride, out_row_stride, out_gen_stride)
     check(L._lib().qf_recode_frames_sel_dev(
         ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
-        _ptr(n_rows) if n_rows is not None else None, _ptr(row_coeffs),
-        _ptr(mix) if mix is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
-        _ptr(out), _ptr(out_coeffs), _ptr(out_len) if out_len is not None else None, _ptr(status)),
+        _opt(n_rows), _ptr(row_coeffs),
+        _opt(mix), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        _ptr(out), _ptr(out_coeffs), _opt(out_len), _ptr(status)),
         "recode_frames_sel")
 
 
@@ -827,17 +767,14 @@ def stream_reset(sel, n_sel, k: int, *, n_max: int, G_src: int, state=None, stor
                  ctx: Optional[Context] = None) -> None:
     """qf_stream_reset_dev: zeroes the rank state (rank_state_bytes(k) bytes),
     store_n and seen of the listed generations, each where it is given."""
-    if state is not None:
-        _need(state, G_src * rank_state_bytes(k), "state (rank_state_bytes(k) per generation)")
-    if store_n is not None:
-        _need(store_n, 4 * G_src, "store_n")
-    if seen is not None:
-        _need(seen, 4 * G_src, "seen")
+    _need(state, G_src * rank_state_bytes(k), "state (rank_state_bytes(k) per generation)")
+    _need(store_n, 4 * G_src, "store_n")
+    _need(seen, 4 * G_src, "seen")
     gs = _gen_sel(sel, n_sel, n_max, G_src)
     ctx = ctx or default_context()
     check(L._lib().qf_stream_reset_dev(
-        ctx.handle, k, ctypes.byref(gs), _ptr(state) if state is not None else None,
-        _ptr(store_n) if store_n is not None else None, _ptr(seen) if seen is not None else None), "stream_reset")
+        ctx.handle, k, ctypes.byref(gs), _opt(state),
+        _opt(store_n), _opt(seen)), "stream_reset")
 
 
 # ---------------------------------------------------------------------------
