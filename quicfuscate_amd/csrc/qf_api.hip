@@ -699,12 +699,15 @@ int decode_cauchy_enc(qf_ctx* ctx, const qf_decode_shape* sh, uint32_t G, const 
         const uint32_t Gc = (uint32_t)std::min<uint64_t>(chunk, G - g0);
         if (synw) {
             ev = prof_begin(ctx, st);
+            const char* wname = nullptr;
             QF_CHECK_HIP(qf::synw_launch(ctx->bs, ctx->num_cus, st, k, r,
                                          ctx->offs_in ? rows : rows + g0 * sh->rows_gen_stride, w + off_syn,
                                          ctx->offs_in ? 0 : sh->rows_gen_stride, (uint64_t)r * Lp, sh->row_stride, Lp, L,
                                          Gc, w + off_map + g0 * ms, ms, ctx->d_zero, d_bound + g0,
-                                         ctx->offs_in ? ctx->offs_in + g0 : nullptr));
-            prof_end(ctx, st, ev, std::string("qf_cauchy_synw_k") + std::to_string(k) + "_r" + std::to_string(r));
+                                         ctx->offs_in ? ctx->offs_in + g0 : nullptr, &wname));
+            // (the kernel that ran: plain passes, pass-major 'X' / 'Y' or the shared-row 'Z')
+            prof_end(ctx, st, ev,
+                     wname ? wname : std::string("qf_cauchy_synw_k") + std::to_string(k) + "_r" + std::to_string(r));
         }
         qf::GatherArgs ga{};
         ga.rows = rows + g0 * sh->rows_gen_stride;

@@ -302,7 +302,8 @@ hipError_t syn_launch(BsCache& cache, int num_cus, hipStream_t st, uint32_t k, u
 hipError_t synw_launch(BsCache& cache, int num_cus, hipStream_t st, uint32_t k, uint32_t r,
                        const uint8_t* rows, uint8_t* syn, uint64_t rgs, uint64_t sgs, uint64_t rs,
                        uint64_t srs, uint32_t L, uint32_t G, const uint8_t* smap, uint32_t map_stride,
-                       const uint8_t* zero, const uint32_t* bound, const uint64_t* rows_offs) {
+                       const uint8_t* zero, const uint32_t* bound, const uint64_t* rows_offs,
+                       const char** name_out) {
     const QfBsEntry* first = find('w', k, r);
     if (!first || map_stride != first->map_stride || !zero) return bs_invalid(__LINE__);
     // an item (128 units) must lie in at most two generations
@@ -321,6 +322,7 @@ hipError_t synw_launch(BsCache& cache, int num_cus, hipStream_t st, uint32_t k, 
         // every pass of the chosen mode reads the slot map at the caller's
         // stride (checked per entry: 'X' / 'Y' / 'Z' are separate specs)
         if (e.map_stride != map_stride) return bs_invalid(__LINE__);
+        if (name_out && e.j0 == 0) *name_out = e.name;
         hipError_t err = launch(cache, &e, num_cus, st, rows, syn + (uint64_t)e.j0 * srs, rgs, sgs, rs, srs, L, G, Lv,
                                 map_stride, smap, zero, nullptr, 0, nullptr, rows_offs, nullptr, bound);
         if (err != hipSuccess) return err;

@@ -5,6 +5,8 @@ original source bytes and equal the oracle's solution; statuses must match
 import numpy as np
 import pytest
 
+from tests import rounds_ref as rr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -76,6 +78,23 @@ def run_decode(qf, k, r, L, G, max_rows, gens, with_coeffs):
     qf.default_context().sync()
     return (t_rec.cpu().numpy(), t_recidx.cpu().numpy().view(np.uint16).reshape(G, -1),
             t_nrec.cpu().numpy(), t_status.cpu().numpy(), rrs, rec_gs)
+
+
+def run_decode_named(qf, *args):
+    """run_decode with the context's kernel timing on: (outputs, names of the
+    kernels that ran)."""
+    ctx = qf.default_context()
+    ctx.sync()
+    ctx.profile(True)
+    try:
+        out = run_decode(qf, *args)
+        return out, set(ctx.kernel_times())
+    finally:
+        ctx.profile(False)
+
+
+def _payload_kernels(names):
+    return {n for n in names if n.startswith("qf_combine_bs") or n.startswith("k_combine_slots")}
 
 
 def check(oracle, k, L, src, gens, out, with_coeffs):
@@ -555,14 +574,18 @@ def test_decode_combine_wide(qf, oracle, gpu_ctx, k, r, L, G, erase, path, wide,
     pass reading two coefficient records per row (qf_combine_bs_r24,
     QF_OPT_COMBINE_WIDE = 1) or as two 16-output passes (0): bit-exact either
     way, on the C5 syndrome path and the general (Gauss-Jordan) path, with
-    generations of e <= 16 (no pass-1 outputs) among them when e is random."""
+    generations of e <= 16 (no pass-1 outputs) among them when e is random.
+    The kernel that ran is the one the setting promises (the 24-output kernel,
+    or the pass-major 16-output one)."""
     _path(monkeypatch, path)
     qf.set_default_options(combine_wide=wide)
     rng = np.random.default_rng(k * 7 + r + L + (erase or 0))
     kw = {"erase": erase, "shuffle": False} if erase is not None else {}
     max_rows = k + r
     src, gens = make_batch(oracle, rng, k, r, L, G, max_rows, **kw)
-    out = run_decode(qf, k, r, L, G, max_rows, gens, False)
+    out, names = run_decode_named(qf, k, r, L, G, max_rows, gens, False)
+    assert _payload_kernels(names) == {rr.cmb_kernel(e_max=min(k, r), wide=wide)}, names
+    assert rr.cmb_kernel(e_max=min(k, r), wide=1) != rr.cmb_kernel(e_max=min(k, r), wide=0)
     check(oracle, k, L, src, gens, out, False)
 
 
@@ -576,34 +599,50 @@ def test_decode_combine_jump_xcd(qf, oracle, gpu_ctx, k, r, L, G, erase, path, j
     M0-indexed XORs (0), pass-major or with the passes of a slot interleaved
     on one XCD (QF_OPT_COMBINE_XCD = 1): bit-exact in every combination, for
     one, two (wide), three and four passes, on the C5 syndrome path and the
-    general (Gauss-Jordan) path."""
+    general (Gauss-Jordan) path.  The payload kernel that ran is the one the
+    combination selects (qf_bs.hip cmb_entry; the fused decode of (64, 16)
+    has no payload pass)."""
     _path(monkeypatch, path)
     qf.set_default_options(combine_jump=jump, combine_xcd=xcd)
     rng = np.random.default_rng(k * 11 + r + L + (erase or 0))
     kw = {"erase": erase, "shuffle": False} if erase is not None else {}
     max_rows = k + r
     src, gens = make_batch(oracle, rng, k, r, L, G, max_rows, **kw)
-    out = run_decode(qf, k, r, L, G, max_rows, gens, False)
+    out, names = run_decode_named(qf, k, r, L, G, max_rows, gens, False)
+    fused = path == "default_1wave" and (k, r) == (64, 16)
+    want = set() if fused else {rr.cmb_kernel(e_max=min(k, r), jump=jump, xcd=xcd)}
+    assert _payload_kernels(names) == want, names
+    # jump changes the kernel at every pass count; xcd where the launch is pass-major in 16-output passes
+    assert rr.cmb_kernel(e_max=min(k, r), jump=1, xcd=xcd) != rr.cmb_kernel(e_max=min(k, r), jump=0, xcd=xcd)
     check(oracle, k, L, src, gens, out, False)
 
 
 @pytest.mark.parametrize("pm24", [1, 0])
 @pytest.mark.parametrize("path", ["default_1wave", "general_bs"])
 @pytest.mark.parametrize("k,r,L,G,erase", [(196, 59, 9000, 5, None), (196, 59, 4100, 6, 39), (160, 48, 4100, 7, 40),
-                                           (128, 39, 2100, 9, 36), (100, 64, 3000, 5, None), (80, 40, 2500, 6, 33)])
+                                           (128, 39, 2100, 9, 36), (100, 64, 3000, 5, None), (80, 40, 2500, 6, 33),
+                                           # every generation needs the third 24-output pass (outputs 48 ..)
+                                           (196, 59, 4100, 5, 55), (196, 59, 4100, 5, 49), (100, 64, 3000, 5, 64)])
 def test_decode_combine_pm24(qf, oracle, gpu_ctx, k, r, L, G, erase, path, pm24, monkeypatch):
-    """A payload pass of 33-64 outputs (e_max) as 24-output passes in one
-    launch (qf_combine_bs_r24_pm_j3, QF_OPT_COMBINE_PM24 = 1; the last pass's
-    pieces past the written records redirected) or as 16-output passes (0):
-    bit-exact either way, random or fixed erasure counts, C5 and general
-    paths, rows that end mid-unit."""
+    """A payload pass of 49-64 outputs (e_max = min(k, r): four record passes)
+    as three 24-output passes in one launch (qf_combine_bs_r24_pm_j3,
+    QF_OPT_COMBINE_PM24 = 1; the last pass's pieces past the written records
+    redirected) or as 16-output passes (0); at e_max <= 48 the setting
+    changes nothing and both run the 16-output pass-major kernel.  Bit-exact
+    either way, random or fixed erasure counts (among them 49, 55 and 64 in
+    every generation: the third 24-output pass), C5 and general paths, rows
+    that end mid-unit; and the kernel that ran is the one the rule gives."""
     _path(monkeypatch, path)
     qf.set_default_options(combine_pm24=pm24)
     rng = np.random.default_rng(k * 13 + r + L + (erase or 0))
     kw = {"erase": erase, "shuffle": False} if erase is not None else {}
     max_rows = k + r
     src, gens = make_batch(oracle, rng, k, r, L, G, max_rows, **kw)
-    out = run_decode(qf, k, r, L, G, max_rows, gens, False)
+    out, names = run_decode_named(qf, k, r, L, G, max_rows, gens, False)
+    e_max = min(k, r)
+    assert _payload_kernels(names) == {rr.cmb_kernel(e_max=e_max, pm24=pm24)}, names
+    # the two settings run different kernels exactly where the rule says they must
+    assert (rr.cmb_kernel(e_max=e_max, pm24=1) != rr.cmb_kernel(e_max=e_max, pm24=0)) == (e_max > 48)
     check(oracle, k, L, src, gens, out, False)
 
 
@@ -615,12 +654,15 @@ def test_decode_c5_synw_shared(qf, oracle, gpu_ctx, k, r, L, G, erase, shared, m
     sharing the row gather through LDS ('Z', QF_OPT_SYNW_SHARED = 1), and
     pass-major ('Y' / plain 'X', 0): bit-exact either way, with few erasures
     (most items then skip the upper passes but still produce their share of
-    the rows) and with many, and a partial last unit (L % 16 != 0)."""
+    the rows) and with many, and a partial last unit (L % 16 != 0).  The
+    syndrome kernel that ran is the one the setting selects."""
     _path(monkeypatch, "default_1wave")
     qf.set_default_options(synw_shared=shared)
     rng = np.random.default_rng(k * 31 + L + (erase or 0))
     kw = {"erase": erase, "shuffle": False} if erase is not None else {}
     max_rows = k + r
     src, gens = make_batch(oracle, rng, k, r, L, G, max_rows, **kw)
-    out = run_decode(qf, k, r, L, G, max_rows, gens, False)
+    out, names = run_decode_named(qf, k, r, L, G, max_rows, gens, False)
+    assert {n for n in names if n.startswith("qf_cauchy_synw")} == {rr.synw_kernel(k, r, shared=shared)}, names
+    assert rr.synw_kernel(k, r, shared=1) != rr.synw_kernel(k, r, shared=0)
     check(oracle, k, L, src, gens, out, False)

@@ -389,10 +389,14 @@ def test_encode_sliding_kernels(qf, oracle, gpu_ctx, k, r, L, sliding):
     """Overlapping generations (adaptive.rs:519-562: a window per source
     packet, generation stride = row stride) through the shapes' sliding-window
     kernels (QF_OPT_SLIDING_KERNELS = 1: cached row loads, (48, 8) as the
-    hybrid FFT pass) or the block kernels (0): every checked window equals the
-    oracle's encode of its k rows, and the batch equals the block layout's
-    encode of the same windows."""
+    hybrid FFT pass) or the block kernels (0): every one of the G windows
+    equals the block layout's encode of its k rows (tails and untouched bytes
+    too: the reuse of cached rows across neighbouring windows, items and
+    workgroups is the kernels' point), 16 seeded windows equal the oracle's
+    encode, and a sliding kernel ran exactly where one exists and is asked for."""
     import torch
+
+    from tests import rounds_ref as rr
 
     qf.set_default_options(sliding_kernels=sliding)
     RS = (L + 15) // 16 * 16 + 16
@@ -401,20 +405,40 @@ def test_encode_sliding_kernels(qf, oracle, gpu_ctx, k, r, L, sliding):
     gen = torch.Generator(device="cuda").manual_seed(k * 7 + L)
     src = torch.randint(0, 256, ((G + k - 1) * RS,), dtype=torch.uint8, device="cuda", generator=gen)
     rep = torch.full((G * r * drs,), 0xA5, dtype=torch.uint8, device="cuda")
-    qf.encode_batch(src, rep, k, r, L, src_row_stride=RS, src_gen_stride=RS, rep_row_stride=drs,
-                    rep_gen_stride=r * drs, G=G, zero_tail=True, ctx=gpu_ctx)
-    wins = [0, 1, 77, G - 1]
-    blk = torch.stack([src.view(-1, RS)[g:g + k] for g in wins]).reshape(-1)
-    rb = torch.full((len(wins) * r * drs,), 0xA5, dtype=torch.uint8, device="cuda")   # same fill: bytes past the tail untouched
-    qf.encode_batch(blk, rb, k, r, L, src_row_stride=RS, src_gen_stride=k * RS, rep_row_stride=drs,
-                    rep_gen_stride=r * drs, G=len(wins), zero_tail=True, ctx=gpu_ctx)
+    torch.cuda.synchronize()
     gpu_ctx.sync()
-    got = rep.view(G, r, drs).cpu().numpy()
-    blk_rep = rb.view(len(wins), r, drs).cpu().numpy()
+    gpu_ctx.profile(True)
+    try:
+        qf.encode_batch(src, rep, k, r, L, src_row_stride=RS, src_gen_stride=RS, rep_row_stride=drs,
+                        rep_gen_stride=r * drs, G=G, zero_tail=True, ctx=gpu_ctx)
+        gpu_ctx.sync()
+        names = set(gpu_ctx.kernel_times())
+    finally:
+        gpu_ctx.profile(False)
+    has_sliding = rr.kernel("g", k, r) is not None
+    assert has_sliding == ((k, r) in {(32, 5), (16, 1), (48, 8)})
+    ran_sliding = {n for n in names if n.endswith("_sl")}
+    if sliding and has_sliding:
+        assert ran_sliding == {rr.kernel("g", k, r)} and names == ran_sliding, names
+    else:
+        assert not ran_sliding and names, names
+    # every window as a generation of its own (300 x k rows, at most ~350 MB)
+    win = torch.arange(G, device="cuda")[:, None] + torch.arange(k, device="cuda")[None, :]
+    blk = src.view(-1, RS)[win].reshape(-1)
+    rb = torch.full((G * r * drs,), 0xA5, dtype=torch.uint8, device="cuda")   # same fill: bytes past the tail untouched
+    torch.cuda.synchronize()
+    qf.encode_batch(blk, rb, k, r, L, src_row_stride=RS, src_gen_stride=k * RS, rep_row_stride=drs,
+                    rep_gen_stride=r * drs, G=G, zero_tail=True, ctx=gpu_ctx)
+    gpu_ctx.sync()
+    torch.cuda.synchronize()
+    same = (rep.view(G, -1) == rb.view(G, -1)).all(dim=1)
+    assert bool(same.all()), ("windows that differ from their block encode", torch.nonzero(~same).flatten()[:16].tolist())
+    rng = np.random.default_rng(k * 7 + L)
+    wins = sorted({0, 1, G - 1, *rng.choice(np.arange(2, G - 1), size=13, replace=False).tolist()})
+    assert len(wins) == 16
     s = src.cpu().numpy()
-    for n, g in enumerate(wins):
+    for g in wins:
         rows = s[g * RS:(g + k) * RS].reshape(k, RS)[:, :L]
         want = oracle.encode(rows, r)
-        ok_s, ok_b = bool((got[g, :, :L] == want).all()), bool((blk_rep[n, :, :L] == want).all())
-        assert ok_s and ok_b, (g, "sliding batch == oracle", ok_s, "block batch == oracle", ok_b)
-    assert (got[wins] == blk_rep).all()   # tails and untouched bytes too
+        got = rep.view(G, r, drs)[g, :, :L].cpu().numpy()
+        assert (got == want).all(), (g, "sliding batch != oracle")
