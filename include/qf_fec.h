@@ -792,6 +792,136 @@ int qf_stream_reset_dev(qf_ctx *ctx, uint32_t k, const qf_gen_sel *sel, uint8_t 
                         uint32_t *store_n_dev, uint32_t *seen_dev);
 
 /* ---------------------------------------------------------------------------
+ * Streaming receive from a flat poll.  No reference counterpart.  A receive
+ * ring delivers frames in arrival order, and the generation of a frame comes
+ * from an outer header (Packet::to_raw carries none).  A flat poll is N frame
+ * slots in that order plus one u32 generation tag per frame; the three calls
+ * below take it to the rank states and the row stores without a host scan and
+ * without a per-generation poll buffer, and touch only the generations the
+ * poll holds:
+ *   qf_parse_poll_headers_dev  the flat poll -> the list of touched generations (sel, n_sel)
+ *                              and, per list entry, row_off, row_len, row_index, n_rows, row_coeffs
+ *   qf_rank_update_sel_batch   the entries' rows against the listed generations' rank states
+ *                              -> innovative; rank_dev[sel[j]] of a persistent rank array
+ *   qf_store_append_sel_dev    take_dev = innovative, src_dev = the poll's frames_dev,
+ *                              src_gen_stride = N_max * frame_stride
+ *   qf_gen_select_dev          over the persistent rank array (QF_SELECT_MARK, seen_dev)
+ *   qf_decode_frames_sel_dev   or qf_recode_frames_sel_dev over the store arrays
+ *   qf_stream_reset_dev        state, store_n and seen of the finished generations, and a
+ *                              second call with seen_dev = rank_dev (state_dev and
+ *                              store_n_dev NULL), which clears their entries of the
+ *                              persistent rank array
+ * ------------------------------------------------------------------------- */
+/* No reference counterpart.  Groups a flat poll by generation, stably, and
+ * parses the headers where the frames lie.
+ * Reads: frames_dev, N_max slots of frame_stride bytes in the payload-aligned
+ * layout of qf_frame_payload_offset(k); frame_len_dev, frame_off_dev (nullable:
+ * 0) and ids_dev per frame as for qf_parse_frame_headers_dev; frame_gen_dev,
+ * one u32 generation tag per frame; n_frames_dev (nullable: N_max), a device
+ * count: the call looks at frames 0 .. N-1, N = min(*n_frames_dev, N_max).  Of
+ * a frame at most the 3 header bytes and the k vector bytes are read, all
+ * inside its slot; no payload byte.
+ * Writes, by list position j in 0..n_max-1:
+ *   sel_dev[j], *n_sel_dev, *n_match_dev (nullable)  the touched generations,
+ *       those with at least one frame tagged < G_src, ascending, the first
+ *       n_max of them; semantics as qf_gen_select_dev (entries at and above
+ *       *n_sel_dev are not written, *n_match_dev counts all touched)
+ *   row_off_dev, row_len_dev, row_index_dev, row_coeffs_dev (max_rows slots
+ *       per entry) and n_rows_dev[j]: byte for byte what
+ *       qf_parse_frame_headers_dev writes for a generation whose frames are
+ *       the entry's frames in arrival order (ascending frame number f), except
+ *       that row_off is relative to frames_dev: f*frame_stride + frame_off + 1
+ *       for a systematic frame, + 3 + k for a coded one.  n_rows_dev[j] = 0 for
+ *       unused entries j >= *n_sel_dev; slots at or above n_rows_dev[j] are
+ *       not written
+ *   entry_status_dev[j]: QF_OK; QF_ETOOSMALL for a generation with more than
+ *       max_rows tagged frames in this poll, valid or not: the entry is listed
+ *       with n_rows 0 and none of its frames is ingested (so the rule does not
+ *       depend on the order of arrival)
+ * and per frame f < N (frames at or above N are not written):
+ *   frame_status_dev[f]: the per-frame codes of qf_parse_frame_headers_dev;
+ *       QF_EINVAL for a tag >= G_src; QF_ENOTREADY for a frame whose
+ *       generation was not listed because the list was full, or whose
+ *       generation has more than max_rows frames: the caller can present those
+ *       frames again.
+ * Every output is deterministic: none depends on the order in which waves or
+ * atomics run.
+ * Returns QF_EINVAL for k outside 1..256, L == 0, max_rows outside 1..1024,
+ * G_src == 0 or > 2^24, n_max == 0, frame_stride % 16 != 0, N_max *
+ * frame_stride > 2^32 (the offsets are u32), a NULL required pointer (all but
+ * frame_off_dev, n_frames_dev and n_match_dev; the per-frame pointers only
+ * when N_max > 0), or frames_dev not 16-byte aligned.
+ * Kernels: k_poll_count (a lane per frame counts its tag), k_gen_select_count
+ * and k_gen_select_scatter over the counts, k_poll_place (a lane per frame
+ * finds its entry and claims one of its slots) and k_poll_headers (a wave per
+ * entry sorts its frames and parses them in order). */
+int qf_parse_poll_headers_dev(qf_ctx *ctx, uint32_t k, uint32_t L, uint32_t max_rows,
+                              const uint8_t *frames_dev, uint64_t frame_stride, uint32_t N_max,
+                              const uint32_t *frame_len_dev, const uint32_t *frame_off_dev,
+                              const uint64_t *ids_dev, const uint32_t *frame_gen_dev,
+                              const uint32_t *n_frames_dev, uint32_t G_src, uint32_t n_max,
+                              uint32_t *sel_dev, uint32_t *n_sel_dev, uint32_t *n_match_dev,
+                              uint16_t *row_index_dev, uint32_t *n_rows_dev, uint8_t *row_coeffs_dev,
+                              uint32_t *row_len_dev, uint32_t *row_off_dev,
+                              int32_t *entry_status_dev, int32_t *frame_status_dev);
+
+/* No reference counterpart.  qf_rank_update_batch over a list: the slots
+ * (row_index_dev, n_rows_dev, row_coeffs_dev) and the outputs innovative_dev,
+ * status_dev and rank_sel_dev (nullable) are compact, indexed by the list
+ * position j in 0..n_max-1 (shape->max_rows slots per entry); state_dev holds
+ * the rank states of sel->G_src generations and is indexed by sel_dev[j], and
+ * so is rank_dev (nullable), of which only rank_dev[sel_dev[j]] of listed
+ * entries is written, so a persistent rank array feeds qf_gen_select_dev.
+ * A listed entry with sel_dev[j] < G_src: flags, status, rank (in both places)
+ * and the state bytes afterwards are byte for byte what qf_rank_update_batch
+ * produces for that generation with the same slots.  An invalid entry gets
+ * status QF_EINVAL, flags 0 and rank_sel 0, and nothing is read or written
+ * through it.  An unused entry gets flags 0, status QF_OK and rank_sel 0.
+ * The list entries must be distinct (the list of qf_parse_poll_headers_dev
+ * is): for a generation listed twice the result is unspecified, but every
+ * access stays in bounds.
+ * Returns what qf_rank_update_batch returns with n_max in the place of G
+ * (status_dev is required, rank_sel_dev and rank_dev are not), and QF_EINVAL
+ * for a NULL sel or sel_dev, n_max == 0 or G_src == 0.
+ * One kernel, k_rank_update_sel: k_rank_filter's resuming form with the list
+ * in front. */
+int qf_rank_update_sel_batch(qf_ctx *ctx, const qf_rank_shape *shape, const qf_gen_sel *sel,
+                             const uint16_t *row_index_dev, const uint32_t *n_rows_dev,
+                             const uint8_t *row_coeffs_dev, uint8_t *state_dev,
+                             uint8_t *innovative_dev, uint32_t *rank_sel_dev, uint32_t *rank_dev,
+                             int32_t *status_dev);
+
+/* No reference counterpart.  qf_store_append_dev over a list: row_off_dev,
+ * row_len_dev, row_index_dev, n_rows_dev, row_coeffs_dev, take_dev and
+ * status_dev are compact, indexed by the list position j (shape->max_rows
+ * slots per entry); the five store arrays and store_n_dev hold sel->G_src
+ * generations and are indexed by sel_dev[j].  All entries' rows lie in one
+ * source region: rows[j][s] = the row_len bytes at src_dev + row_off (what
+ * qf_parse_poll_headers_dev leaves, with src_dev = its frames_dev), and
+ * shape->src_gen_stride is that region's size in bytes, so the geometry rule
+ * reads row_off + row_len > src_gen_stride -> QF_EINVAL.  No payload is copied
+ * before the append.
+ * A listed entry with sel_dev[j] < G_src: status, the appended bytes and
+ * metadata and store_n_dev are byte for byte what qf_store_append_dev writes
+ * for that generation with the same slots; QF_ETOOSMALL, "a generation that is
+ * not QF_OK appends nothing" and the read and write rules are that call's.  An
+ * invalid entry gets status QF_EINVAL and nothing is read or written through
+ * it; an unused entry gets status QF_OK.  The list entries must be distinct:
+ * for a generation listed twice the result is unspecified, but every access
+ * stays in bounds.
+ * Returns what qf_store_append_dev returns with n_max in the place of G, and
+ * QF_EINVAL for a NULL sel or sel_dev, n_max == 0 or G_src == 0.
+ * Two kernels: k_store_prepare_sel and k_store_rows_sel, the dense call's with
+ * the list in front. */
+int qf_store_append_sel_dev(qf_ctx *ctx, const qf_store_shape *shape, const qf_gen_sel *sel,
+                            const uint8_t *src_dev, const uint32_t *row_off_dev,
+                            const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                            const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                            const uint8_t *take_dev, uint8_t *store_dev, uint32_t *store_off_dev,
+                            uint32_t *store_len_dev, uint16_t *store_index_dev,
+                            uint8_t *store_coeffs_dev, uint32_t *store_n_dev, int32_t *status_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations
@@ -1143,6 +1273,16 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
  * and, once rank_dev[g] reaches k (a relay may recode sooner):
  *   qf_decode_frames_dev        over the store arrays, max_rows = cap, src_gen_stride = store_gen_stride
  *   qf_recode_frames_dev        the same at a relay (cap <= 255)
+ * The same from a flat poll (frames in arrival order, one generation tag per
+ * frame), touching the poll's generations only and with no host sort:
+ *   qf_parse_poll_headers_dev   the flat poll -> the list of touched generations and, per entry,
+ *                               row_off, row_len, row_index, n_rows, row_coeffs
+ *   qf_rank_update_sel_batch    the listed generations' rank states; rank_dev is persistent
+ *   qf_store_append_sel_dev     src_dev = the flat poll's frames_dev
+ * then qf_gen_select_dev over the persistent rank_dev, the listed decode or
+ * recode, and qf_stream_reset_dev twice: once for state_dev, store_n_dev and
+ * seen_dev, once more with seen_dev = rank_dev (the other two NULL), which
+ * clears the listed generations' ranks.
  * The intermediate rows belong to the caller.
  * ------------------------------------------------------------------------- */
 /* No reference counterpart (a layout rule): P = round_up(3 + k, 16) for k in

@@ -245,6 +245,12 @@ _SIGS = {
     "qf_recode_frames_sel_dev": (_I, [_P, ctypes.POINTER(RecodeFramesShape), ctypes.POINTER(GenSel), _P, _P, _P, _P,
                                       _P, _P, _P, _U64, _P, _P, _P, _P]),
     "qf_stream_reset_dev": (_I, [_P, _U32, ctypes.POINTER(GenSel), _P, _P, _P]),
+    "qf_parse_poll_headers_dev": (_I, [_P, _U32, _U32, _U32, _P, _U64, _U32, _P, _P, _P, _P, _P, _U32, _U32, _P, _P,
+                                       _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_rank_update_sel_batch": (_I, [_P, ctypes.POINTER(RankShape), ctypes.POINTER(GenSel), _P, _P, _P, _P, _P, _P,
+                                      _P, _P]),
+    "qf_store_append_sel_dev": (_I, [_P, ctypes.POINTER(StoreShape), ctypes.POINTER(GenSel), _P, _P, _P, _P, _P, _P,
+                                     _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

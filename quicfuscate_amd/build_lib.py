@@ -30,7 +30,8 @@ LIB = OUT_DIR / "libqf_fec.so"
 LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
-           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip", "qf_select.hip"]
+           "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip", "qf_select.hip",
+           "qf_poll.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -159,9 +160,9 @@ RESOURCE_RULES = {
     "qf_recode.hip": _Rule(("k_recode_prepare",), None, every=True),
     # k_rank_filter keeps the incoming vector in registers and the basis in LDS
     # (DESIGN.md 3.10): no scratch, in the one-call instantiations (1 .. 4
-    # columns per lane) and in the four that resume from a rank state
-    # 
-    "qf_rank.hip": _Rule(("k_rank_filter",), 8, every=True),
+    # columns per lane), in the four that resume from a rank state
+    #  and in the four that do so over a list
+    "qf_rank.hip": _Rule(("k_rank_filter",), 12, every=True),
     # the framing kernels of coded rows hold a few addresses and one 16-byte
     # block per lane: no scratch
     "qf_wire.hip": _Rule(("k_frame_rows", "k_parse_frames_coded", "k_parse_frame_headers"), 3),
@@ -172,11 +173,15 @@ RESOURCE_RULES = {
     # a source map for the calls over a list
     "qf_relay.hip": _Rule(("k_combine_rows_at",), 3),
     # the row store's control and payload passes hold a few addresses and one
-    # 16-byte unit per lane: no scratch
-    "qf_store.hip": _Rule(("k_store_prepare", "k_store_rows"), 2),
+    # 16-byte unit per lane: no scratch, in the dense call's
+    # two and in the two over a list
+    "qf_store.hip": _Rule(("k_store_prepare", "k_store_rows"), 4),
     # the list kernels hold a few counters or one 16-byte unit per lane
     # (DESIGN.md 3.15): no scratch
     "qf_select.hip": _Rule(("k_gen_select_count", "k_gen_select_scatter", "k_sel_gather", "k_stream_reset"), 4),
+    # the flat poll's kernels hold a few counters and addresses and one 16-byte
+    # block per lane: no scratch
+    "qf_poll.hip": _Rule(("k_poll_count", "k_poll_place", "k_poll_headers"), 3),
 }
 # the sources compiled with resource-usage remarks
 REMARK_SOURCES = ("qf_gf16_bs.hip", *RESOURCE_RULES)

@@ -84,6 +84,15 @@ struct RowArrays {
 QF_LOCAL hipError_t launch_rank(qf_ctx* ctx, const RowArrays& rows, uint32_t k, uint32_t r, uint32_t max_rows,
                                 uint32_t G, uint8_t* state, uint8_t* innovative, uint32_t* rank, int32_t* status,
                                 hipStream_t st);
+// The two kernels of qf_gen_select_dev over any device array of G <= 2^24
+// counts, without the seen condition: the first n_max entries >= min_rank,
+// ascending, to sel, their number to *n_sel and the number of all to *n_match
+// (nullable).  counts: gen_select_work_bytes(G) bytes of scratch.
+// (qf_select.hip; the flat poll's list, qf_poll.hip)
+QF_LOCAL size_t gen_select_work_bytes(uint32_t G);
+QF_LOCAL hipError_t launch_gen_select_list(const uint32_t* rank, uint32_t G, uint32_t min_rank, uint32_t n_max,
+                                           uint32_t* counts, uint32_t* sel, uint32_t* n_sel, uint32_t* n_match,
+                                           hipStream_t st);
 // The fields of k_decode_prepare's arguments that follow from the rows and the
 // shape alike for every caller: the row arrays, the tables, k, e_max, e_lds,
 // max_rows, max_rows_pad, passes and G.  The outputs, accept, coef_gen_stride,

@@ -301,6 +301,19 @@ struct RankUpdateArgs : RankFilterArgs {
 size_t rank_state_bytes(uint32_t k);   // 0 for k outside 1..256
 hipError_t launch_rank_update(const RankUpdateArgs& a, hipStream_t st);
 
+// The resumed walk over a list (qf_rank_update_sel_batch): G
+// is the list's n_max, the slots and the outputs are indexed by the list
+// position j, state by the listed generation sel[j] < G_src, and rank_dense
+// (nullable) receives rank_dense[sel[j]] of the listed entries only.  Its own
+// argument type, so the dense calls' kernels keep their arguments.
+struct RankUpdateSelArgs : RankUpdateArgs {
+    const uint32_t* sel;
+    const uint32_t* n_sel;       // nullptr: G
+    uint32_t* rank_dense;        // [G_src] or nullptr
+    uint32_t G_src;
+};
+hipError_t launch_rank_update_sel(const RankUpdateSelArgs& a, hipStream_t st);
+
 // One encoder window of a multi-connection send batch: the window's ring at
 // src + src_off (position i in slot (rot + i) % k), its repairs at
 // rep + rep_off, rows rep_row_stride apart.

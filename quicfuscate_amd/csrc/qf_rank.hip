@@ -35,7 +35,9 @@
 //                  Its second form (qf_rank_update_batch) restores U, B and
 //                  piv from a per-generation rank state in HBM first and
 //                  writes them back when the rank grew, so a generation
-//                  fills over many calls.
+//                  fills over many calls.  Its third form
+//                  (qf_rank_update_sel_batch) does so for the generations of
+//                  a list only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -195,8 +197,9 @@ size_t rank_filter_lds_bytes(uint32_t k) { return rank_hdr(k) + (size_t)k * rank
 //       ceil(nb / 4) groups are valid.
 // colst and pivrow follow from U and piv; first, lfac, stage and later are
 // scratch of one call.
-template <bool STATE> struct RankArgsOf { typedef RankFilterArgs type; };
-template <> struct RankArgsOf<true> { typedef RankUpdateArgs type; };
+template <bool STATE, bool SEL = false> struct RankArgsOf { typedef RankFilterArgs type; };
+template <> struct RankArgsOf<true, false> { typedef RankUpdateArgs type; };
+template <> struct RankArgsOf<true, true> { typedef RankUpdateSelArgs type; };
 constexpr uint32_t kStateMagic = 0x53524651u;   // "QFRS"
 constexpr uint32_t kStateUnits = 16, kStatePiv = 48;
 __host__ __device__ inline uint32_t rank_state_basis(uint32_t k) { return kStatePiv + rank_kc(k); }
@@ -207,20 +210,43 @@ __host__ __device__ inline uint32_t rank_state_size(uint32_t k) {
 // NQ = ceil(k / 64) columns per lane.  STATE: the span is resumed from and
 // written back to a.state (the arguments are RankUpdateArgs; timed as
 // k_rank_update); without it every added block drops out and the code is the
-// one-call filter's, instruction for instruction.
-template <int NQ, bool STATE>
-__global__ void __launch_bounds__(64) k_rank_filter(typename RankArgsOf<STATE>::type a) {
+// one-call filter's, instruction for instruction.  SEL (with STATE; the
+// arguments are RankUpdateSelArgs, timed as k_rank_update_sel):
+// the block is list entry g of a.G = n_max, its slots and outputs are indexed
+// by g, and the state and the dense rank array by the listed generation gs,
+// the only two places where that number is used.  Without SEL gs is g and the
+// code is what it was.
+template <int NQ, bool STATE, bool SEL = false>
+__global__ void __launch_bounds__(64) k_rank_filter(typename RankArgsOf<STATE, SEL>::type a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const uint32_t g = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     const uint32_t k = a.k, mr = a.max_rows;
+    uint32_t gs = g;
+    if constexpr (SEL) {
+        uint32_t n_used = a.G;
+        if (a.n_sel) n_used = min(*a.n_sel, n_used);
+        // an unused entry's sel value is not looked at; nothing is read or
+        // written through an invalid one
+        const bool unused = g >= n_used;
+        if (!unused) gs = a.sel[g];
+        if (unused || gs >= a.G_src) {
+            if (a.innovative)
+                for (uint32_t s = lane; s < mr; s += 64) a.innovative[(uint64_t)g * mr + s] = 0;
+            if (lane == 0) {
+                if (a.rank) a.rank[g] = 0;
+                if (a.status) a.status[g] = unused ? QF_OK : QF_EINVAL;
+            }
+            return;
+        }
+    }
     uint32_t nu0 = 0, nb0 = 0;   // what the state held; rank0 = nu0 + nb0
     uint32_t rank0 = 0;
     uint8_t* sg = nullptr;
     if constexpr (STATE) {
         // The header decides, before anything else is read: an idle generation
         // (no slot in this call) and an invalid state cost these 16 bytes.
-        sg = a.state + (uint64_t)g * rank_state_size(k);
+        sg = a.state + (uint64_t)gs * rank_state_size(k);
         const uint4 h = *reinterpret_cast<const uint4*>(sg);
         const bool empty = (h.x | h.y | h.z | h.w) == 0;
         const bool valid = empty || (h.x == kStateMagic && h.y == k && h.z <= k && h.w <= k && h.z + h.w <= k);
@@ -235,6 +261,9 @@ __global__ void __launch_bounds__(64) k_rank_filter(typename RankArgsOf<STATE>::
                 for (uint32_t s = lane; s < mr; s += 64) a.innovative[(uint64_t)g * mr + s] = 0;
             if (lane == 0) {
                 if (a.rank) a.rank[g] = rank0;
+                if constexpr (SEL) {
+                    if (a.rank_dense) a.rank_dense[gs] = rank0;
+                }
                 if (a.status) a.status[g] = valid ? QF_OK : QF_EINVAL;
             }
             return;
@@ -476,6 +505,9 @@ __global__ void __launch_bounds__(64) k_rank_filter(typename RankArgsOf<STATE>::
     }
     if (lane == 0) {
         if (a.rank) a.rank[g] = nu + nb;
+        if constexpr (SEL) {
+            if (a.rank_dense) a.rank_dense[gs] = nu + nb;
+        }
         if (a.status) a.status[g] = status;
     }
 }
@@ -526,6 +558,20 @@ hipError_t launch_rank_update(const RankUpdateArgs& a, hipStream_t st) {
         case 2: return launch_rank_nq<2, RankUpdateArgs>(k_rank_filter<2, true>, a, lds, st);
         case 3: return launch_rank_nq<3, RankUpdateArgs>(k_rank_filter<3, true>, a, lds, st);
         default: return launch_rank_nq<4, RankUpdateArgs>(k_rank_filter<4, true>, a, lds, st);
+    }
+}
+
+hipError_t launch_rank_update_sel(const RankUpdateSelArgs& a, hipStream_t st) {
+    if (a.G == 0) return hipSuccess;
+    if (a.k == 0 || a.k > 256 || a.max_rows == 0 || a.max_rows > 4096 || !a.state || !a.sel || a.G_src == 0 ||
+        (!a.row_coeffs && a.r && a.k + a.r > 256))
+        return hipErrorInvalidValue;
+    const size_t lds = rank_filter_lds_bytes(a.k);
+    switch ((a.k + 63) / 64) {
+        case 1: return launch_rank_nq<1, RankUpdateSelArgs>(k_rank_filter<1, true, true>, a, lds, st);
+        case 2: return launch_rank_nq<2, RankUpdateSelArgs>(k_rank_filter<2, true, true>, a, lds, st);
+        case 3: return launch_rank_nq<3, RankUpdateSelArgs>(k_rank_filter<3, true, true>, a, lds, st);
+        default: return launch_rank_nq<4, RankUpdateSelArgs>(k_rank_filter<4, true, true>, a, lds, st);
     }
 }
 
@@ -629,4 +675,38 @@ extern "C" int qf_rank_update_batch(qf_ctx* ctx, const qf_rank_shape* sh, uint32
                                     const uint32_t* n_rows, const uint8_t* row_coeffs, uint8_t* state,
                                     uint8_t* innovative, uint32_t* rank, int32_t* status) {
     return rank_run(ctx, sh, G, row_index, n_rows, row_coeffs, true, state, innovative, rank, status);
+}
+
+extern "C" int qf_rank_update_sel_batch(qf_ctx* ctx, const qf_rank_shape* sh, const qf_gen_sel* sel,
+                                        const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                                        uint8_t* state, uint8_t* innovative, uint32_t* rank_sel, uint32_t* rank,
+                                        int32_t* status) {
+    if (!ctx || !sh || !sel || !sel->sel_dev || sel->n_max == 0 || sel->G_src == 0) return QF_EINVAL;
+    const uint32_t k = sh->k, r = sh->r, max_rows = sh->max_rows;
+    if (k == 0 || k > 256 || max_rows == 0 || max_rows > 4096 || sh->flags != 0) return QF_EINVAL;
+    if (!row_coeffs && r && (uint64_t)k + r > 256) return QF_ERANGE;
+    if (!row_index || !status || !state || !aligned16(state)) return QF_EINVAL;
+    std::unique_lock<std::mutex> lk;
+    int s = qf::ctx_lock(ctx, lk);
+    if (s) return s;
+    hipStream_t st = qf::ctx_stream(ctx);
+    qf::RankUpdateSelArgs fa{};
+    fa.row_index = row_index;
+    fa.n_rows = n_rows;
+    fa.row_coeffs = row_coeffs;
+    fa.explog = qf::ctx_explog(ctx);
+    fa.innovative = innovative;
+    fa.rank = rank_sel;
+    fa.status = status;
+    fa.k = k;
+    fa.r = r;
+    fa.max_rows = max_rows;
+    fa.G = sel->n_max;
+    fa.state = state;
+    fa.sel = sel->sel_dev;
+    fa.n_sel = sel->n_sel_dev;
+    fa.rank_dense = rank;
+    fa.G_src = sel->G_src;
+    QF_PROFILED(ctx, st, "k_rank_update_sel", qf::launch_rank_update_sel(fa, st));
+    return QF_OK;
 }

@@ -225,6 +225,24 @@ static hipError_t launch_gen_select(const GenSelectArgs& a, uint32_t blocks, hip
     return hipGetLastError();
 }
 
+size_t gen_select_work_bytes(uint32_t G) { return (size_t)((G + kSelPerBlock - 1) / kSelPerBlock) * 4; }
+
+hipError_t launch_gen_select_list(const uint32_t* rank, uint32_t G, uint32_t min_rank, uint32_t n_max,
+                                  uint32_t* counts, uint32_t* sel, uint32_t* n_sel, uint32_t* n_match,
+                                  hipStream_t st) {
+    if (G == 0 || G > (1u << 24) || n_max == 0 || !rank || !counts || !sel || !n_sel) return hipErrorInvalidValue;
+    GenSelectArgs a{};
+    a.rank = rank;
+    a.counts = counts;
+    a.sel = sel;
+    a.n_sel = n_sel;
+    a.n_match = n_match;
+    a.G = G;
+    a.min_rank = min_rank;
+    a.n_max = n_max;
+    return launch_gen_select(a, (G + kSelPerBlock - 1) / kSelPerBlock, st);
+}
+
 hipError_t launch_sel_gather(const SelGatherArgs& a, hipStream_t st) {
     if (a.n_max == 0) return hipSuccess;
     if (!a.sel || a.k == 0 || a.k > 256 || a.max_rows == 0 || a.max_rows > 1024 || a.G_src == 0)

@@ -17,10 +17,15 @@
 //                   unit ends after one or two loads; the others load the
 //                   unit (masked to the row's bytes, so the tail of the last
 //                   unit is zero) and store it.
+// Both kernels have a second form over a list (qf_store_append_sel_dev, timed
+// as k_store_prepare_sel / k_store_rows_sel): the rows of all
+// entries lie in one flat poll buffer and the stores are the listed
+// generations'.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "qf_fec.h"
 #include "qf_gf_dev.h"
@@ -59,13 +64,48 @@ struct StoreRowsArgs {
     uint32_t max_rows, Lu;
 };
 
-__global__ void __launch_bounds__(64) k_store_prepare(StorePrepareArgs a) {
+// The calls over a list (qf_store_append_sel_dev): the blocks
+// are the n_max list entries; rows, take, status, rec and gen are indexed by
+// the list position, the store arrays and store_n by the listed generation
+// sel[j] < G_src.  Their own argument types, so the dense call's kernels keep
+// their arguments.
+struct StorePrepareSelArgs : StorePrepareArgs {
+    const uint32_t* sel;
+    const uint32_t* n_sel;      // nullptr: n_max
+    uint32_t n_max, G_src;
+};
+
+struct StoreRowsSelArgs : StoreRowsArgs {
+    const uint32_t* sel;        // read for entries with taken rows only: those are listed and valid
+};
+
+// SEL: g is a list entry and gs its generation, which indexes the store side
+// only; without SEL gs is g and the code is the dense call's.
+template <bool SEL>
+__global__ void __launch_bounds__(64)
+k_store_prepare(typename std::conditional<SEL, StorePrepareSelArgs, StorePrepareArgs>::type a) {
     __shared__ uint32_t src_of[64];   // taken ordinal inside the chunk -> its lane
     const uint32_t g = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     const uint32_t mr = a.max_rows;
+    uint32_t gs = g;
+    if constexpr (SEL) {
+        uint32_t n_used = a.n_max;
+        if (a.n_sel) n_used = min(*a.n_sel, n_used);
+        // an unused entry's sel value is not looked at; nothing is read or
+        // written through an invalid one
+        const bool unused = g >= n_used;
+        if (!unused) gs = a.sel[g];
+        if (unused || gs >= a.G_src) {
+            if (lane == 0) {
+                a.status[g] = unused ? QF_OK : QF_EINVAL;
+                a.gen[g] = make_uint2(0, 0);
+            }
+            return;
+        }
+    }
     const uint32_t n = a.n_rows ? a.n_rows[g] : mr;
-    const uint32_t c0 = a.store_n[g];
+    const uint32_t c0 = a.store_n[gs];
     const uint64_t in0 = (uint64_t)g * mr;
     int32_t status = QF_OK;
     uint32_t taken = 0;
@@ -92,7 +132,7 @@ __global__ void __launch_bounds__(64) k_store_prepare(StorePrepareArgs a) {
         }
         return;
     }
-    const uint64_t out0 = (uint64_t)g * a.cap;
+    const uint64_t out0 = (uint64_t)gs * a.cap;
     const bool words = (a.k & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.row_coeffs) |
                                            reinterpret_cast<uintptr_t>(a.store_coeffs)) & 3) == 0;
     const uint32_t per = words ? a.k / 4 : a.k;   // copy steps of one vector
@@ -124,12 +164,14 @@ __global__ void __launch_bounds__(64) k_store_prepare(StorePrepareArgs a) {
     }
     if (lane == 0) {
         a.status[g] = QF_OK;
-        a.store_n[g] = c0 + taken;
+        a.store_n[gs] = c0 + taken;
         a.gen[g] = make_uint2(c0, taken);
     }
 }
 
-__global__ void __launch_bounds__(256) k_store_rows(StoreRowsArgs a) {
+template <bool SEL>
+__global__ void __launch_bounds__(256)
+k_store_rows(typename std::conditional<SEL, StoreRowsSelArgs, StoreRowsArgs>::type a) {
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t f = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; f < a.total; f += step) {
         const uint64_t row = f / a.Lu;   // g * max_rows + j
@@ -140,8 +182,15 @@ __global__ void __launch_bounds__(256) k_store_rows(StoreRowsArgs a) {
         if (j >= gn.y) continue;
         const uint2 r = a.rec[row];      // {row_off, row_len}
         if (r.y <= u16) continue;        // no byte of the row in this unit
-        const uint4 x = load_row_unit(a.src + g * a.src_gen_stride + r.x + u16, r.y, u16);
-        *reinterpret_cast<uint4*>(a.store + g * a.store_gen_stride + (uint64_t)(gn.x + j) * a.store_row_stride + u16) = x;
+        if constexpr (SEL) {
+            // every entry's rows lie in the one region at a.src; the store is the listed generation's
+            const uint4 x = load_row_unit(a.src + r.x + u16, r.y, u16);
+            const uint64_t gs = a.sel[g];
+            *reinterpret_cast<uint4*>(a.store + gs * a.store_gen_stride + (uint64_t)(gn.x + j) * a.store_row_stride + u16) = x;
+        } else {
+            const uint4 x = load_row_unit(a.src + g * a.src_gen_stride + r.x + u16, r.y, u16);
+            *reinterpret_cast<uint4*>(a.store + g * a.store_gen_stride + (uint64_t)(gn.x + j) * a.store_row_stride + u16) = x;
+        }
     }
 }
 
@@ -149,11 +198,13 @@ __global__ void __launch_bounds__(256) k_store_rows(StoreRowsArgs a) {
 
 }  // namespace qf
 
-extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32_t G, const uint8_t* src,
-                                   const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
-                                   const uint32_t* n_rows, const uint8_t* row_coeffs, const uint8_t* take,
-                                   uint8_t* store, uint32_t* store_off, uint32_t* store_len, uint16_t* store_index,
-                                   uint8_t* store_coeffs, uint32_t* store_n, int32_t* status) {
+// qf_store_append_dev over G generations, and with `sel` qf_store_append_sel_dev
+// over its n_max entries (G = n_max).
+static int store_append_run(qf_ctx* ctx, const qf_store_shape* sh, uint32_t G, const qf_gen_sel* sel,
+                            const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                            const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                            const uint8_t* take, uint8_t* store, uint32_t* store_off, uint32_t* store_len,
+                            uint16_t* store_index, uint8_t* store_coeffs, uint32_t* store_n, int32_t* status) {
     if (!ctx || !sh) return QF_EINVAL;
     const uint32_t k = sh->k, L = sh->L, max_rows = sh->max_rows, cap = sh->cap;
     if (k == 0 || k > 256 || L == 0 || max_rows == 0 || max_rows > 1024 || cap == 0 || cap > 1024 ||
@@ -181,7 +232,7 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     uint8_t* w = nullptr;
     s = qf::ctx_work(ctx, wl.size(), &w);
     if (s) return s;
-    qf::StorePrepareArgs pa{};
+    qf::StorePrepareSelArgs pa{};
     pa.row_off = row_off;
     pa.row_len = row_len;
     pa.row_index = row_index;
@@ -202,9 +253,18 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     pa.L = L;
     pa.max_rows = max_rows;
     pa.cap = cap;
-    QF_PROFILED(ctx, st, "k_store_prepare",
-                qf::launch_kernel(qf::k_store_prepare, dim3(G), dim3(64), 0, st, pa));
-    qf::StoreRowsArgs ra{};
+    if (sel) {
+        pa.sel = sel->sel_dev;
+        pa.n_sel = sel->n_sel_dev;
+        pa.n_max = sel->n_max;
+        pa.G_src = sel->G_src;
+        QF_PROFILED(ctx, st, "k_store_prepare_sel",
+                    qf::launch_kernel(qf::k_store_prepare<true>, dim3(G), dim3(64), 0, st, pa));
+    } else {
+        QF_PROFILED(ctx, st, "k_store_prepare",
+                    qf::launch_kernel(qf::k_store_prepare<false>, dim3(G), dim3(64), 0, st, pa));
+    }
+    qf::StoreRowsSelArgs ra{};
     ra.src = src;
     ra.store = store;
     ra.rec = pa.rec;
@@ -219,6 +279,32 @@ extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32
     const uint64_t need = (ra.total + 255) / 256;
     const uint64_t most = (uint64_t)(qf::ctx_num_cus(ctx) > 0 ? qf::ctx_num_cus(ctx) : 1) * 64;
     const dim3 grid((uint32_t)(need < most ? need : most));
-    QF_PROFILED(ctx, st, "k_store_rows", qf::launch_kernel(qf::k_store_rows, grid, dim3(256), 0, st, ra));
+    if (sel) {
+        ra.sel = sel->sel_dev;
+        QF_PROFILED(ctx, st, "k_store_rows_sel", qf::launch_kernel(qf::k_store_rows<true>, grid, dim3(256), 0, st, ra));
+    } else {
+        QF_PROFILED(ctx, st, "k_store_rows", qf::launch_kernel(qf::k_store_rows<false>, grid, dim3(256), 0, st, ra));
+    }
     return QF_OK;
 }
+
+extern "C" int qf_store_append_dev(qf_ctx* ctx, const qf_store_shape* sh, uint32_t G, const uint8_t* src,
+                                   const uint32_t* row_off, const uint32_t* row_len, const uint16_t* row_index,
+                                   const uint32_t* n_rows, const uint8_t* row_coeffs, const uint8_t* take,
+                                   uint8_t* store, uint32_t* store_off, uint32_t* store_len, uint16_t* store_index,
+                                   uint8_t* store_coeffs, uint32_t* store_n, int32_t* status) {
+    return store_append_run(ctx, sh, G, nullptr, src, row_off, row_len, row_index, n_rows, row_coeffs, take, store,
+                            store_off, store_len, store_index, store_coeffs, store_n, status);
+}
+
+extern "C" int qf_store_append_sel_dev(qf_ctx* ctx, const qf_store_shape* sh, const qf_gen_sel* sel,
+                                       const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                                       const uint16_t* row_index, const uint32_t* n_rows, const uint8_t* row_coeffs,
+                                       const uint8_t* take, uint8_t* store, uint32_t* store_off, uint32_t* store_len,
+                                       uint16_t* store_index, uint8_t* store_coeffs, uint32_t* store_n,
+                                       int32_t* status) {
+    if (!sel || !sel->sel_dev || sel->n_max == 0 || sel->G_src == 0) return QF_EINVAL;
+    return store_append_run(ctx, sh, sel->n_max, sel, src, row_off, row_len, row_index, n_rows, row_coeffs, take,
+                            store, store_off, store_len, store_index, store_coeffs, store_n, status);
+}
+

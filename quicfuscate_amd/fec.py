@@ -777,6 +777,96 @@ def stream_reset(sel, n_sel, k: int, *, n_max: int, G_src: int, state=None, stor
         _opt(store_n), _opt(seen)), "stream_reset")
 
 
+def parse_poll_headers(frames, frame_len, ids, frame_gen, sel, n_sel, row_index, n_rows, row_coeffs, row_len, row_off,
+                       entry_status, frame_status, k: int, Lb: int, *, max_rows: int, frame_stride: int, N_max: int,
+                       G_src: int, n_max: int, n_frames=None, frame_off=None, n_match=None,
+                       ctx: Optional[Context] = None) -> None:
+    """qf_parse_poll_headers_dev: a flat poll (N_max frame slots in arrival
+    order, frame_gen[f] the generation tag of frame f, n_frames[0] the frames
+    to look at) grouped by generation and parsed where the frames lie.  sel /
+    n_sel / n_match receive the touched generations as gen_select's list; the
+    row arrays are indexed by the list position ([n_max, max_rows]) and are
+    what parse_frame_headers leaves for the entry's frames in arrival order,
+    with row_off relative to frames.  entry_status: [n_max]; frame_status:
+    [N_max]."""
+    _need(frames, N_max * frame_stride, "frames")
+    _need(frame_len, 4 * N_max, "frame_len")
+    _need(ids, 8 * N_max, "ids")
+    _need(frame_gen, 4 * N_max, "frame_gen")
+    _need(frame_off, 4 * N_max, "frame_off")
+    _need(n_frames, 4, "n_frames")
+    _need(sel, 4 * n_max, "sel")
+    _need(n_sel, 4, "n_sel")
+    _need(n_match, 4, "n_match")
+    _need_rows(n_max, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
+    _need(entry_status, 4 * n_max, "entry_status")
+    _need(frame_status, 4 * N_max, "frame_status")
+    ctx = ctx or default_context()
+    check(L._lib().qf_parse_poll_headers_dev(
+        ctx.handle, k, Lb, max_rows, _ptr(frames), frame_stride, N_max, _ptr(frame_len),
+        _opt(frame_off), _ptr(ids), _ptr(frame_gen),
+        _opt(n_frames), G_src, n_max, _ptr(sel), _ptr(n_sel),
+        _opt(n_match),
+        _ptr(row_index), _ptr(n_rows), _ptr(row_coeffs), _ptr(row_len), _ptr(row_off), _ptr(entry_status),
+        _ptr(frame_status)), "parse_poll_headers")
+
+
+def rank_update_sel_batch(sel, n_sel, row_index, state, status, k: int, *, r: int = 0, max_rows: int, n_max: int,
+                          G_src: int, n_rows=None, row_coeffs=None, innovative=None, rank_sel=None, rank=None,
+                          ctx: Optional[Context] = None) -> None:
+    """qf_rank_update_sel_batch: rank_update_batch over a list.  The slots
+    (row_index, n_rows, row_coeffs) and innovative, status and rank_sel are
+    indexed by the list position; state (G_src * rank_state_bytes(k) bytes) and
+    rank ([G_src], only the listed entries' are written) by sel[j]."""
+    _need_rows(n_max, max_rows, k, None, None, row_index, row_coeffs, n_rows)
+    _need(state, G_src * rank_state_bytes(k), "state (rank_state_bytes(k) per generation)")
+    _need(status, 4 * n_max, "status")
+    _need(innovative, n_max * max_rows, "innovative")
+    _need(rank_sel, 4 * n_max, "rank_sel")
+    _need(rank, 4 * G_src, "rank")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    sh = L.RankShape(k, r, max_rows, 0)
+    check(L._lib().qf_rank_update_sel_batch(
+        ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(row_index),
+        _opt(n_rows),
+        _opt(row_coeffs),
+        _ptr(state),
+        _opt(innovative),
+        _opt(rank_sel),
+        _opt(rank),
+        _ptr(status)), "rank_update_sel_batch")
+
+
+def store_append_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, store, store_off, store_len,
+                     store_index, store_coeffs, store_n, status, k: int, Lb: int, *, max_rows: int, cap: int,
+                     src_bytes: int, store_row_stride: int, store_gen_stride: int, n_max: int, G_src: int,
+                     n_rows=None, take=None, ctx: Optional[Context] = None) -> None:
+    """qf_store_append_sel_dev: store_append over a list.  The rows (row_off
+    relative to src, the flat poll's frames of src_bytes bytes), take and
+    status are indexed by the list position; the five store arrays and store_n
+    hold G_src generations and are indexed by sel[j]."""
+    _need(src, src_bytes, "src")
+    _need_rows(n_max, max_rows, k, row_off, row_len, row_index, row_coeffs, n_rows)
+    _need(store, _span(G_src, store_gen_stride, cap, store_row_stride, (Lb + 15) // 16 * 16), "store")
+    _need(store_off, 4 * G_src * cap, "store_off")
+    _need(store_len, 4 * G_src * cap, "store_len")
+    _need(store_index, 2 * G_src * cap, "store_index")
+    _need(store_coeffs, G_src * cap * k, "store_coeffs")
+    _need(store_n, 4 * G_src, "store_n")
+    _need(status, 4 * n_max, "status")
+    _need(take, n_max * max_rows, "take")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    sh = L.StoreShape(k, Lb, max_rows, cap, 0, 0, src_bytes, store_row_stride, store_gen_stride)
+    check(L._lib().qf_store_append_sel_dev(
+        ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
+        _opt(n_rows), _ptr(row_coeffs),
+        _opt(take),
+        _ptr(store), _ptr(store_off), _ptr(store_len), _ptr(store_index), _ptr(store_coeffs), _ptr(store_n),
+        _ptr(status)), "store_append_sel")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
