@@ -38,6 +38,8 @@ extern "C" {
 #define QF_EDEVICE (-5)    /* HIP runtime error                                  */
 #define QF_ENOMEM (-6)     /* allocation failed                                  */
 #define QF_ETOOSMALL (-7)  /* output buffer too short (quiche BufferTooShort)    */
+#define QF_ESTALE (-8)     /* frame older than the generation its slot now holds */
+#define QF_ECLOSED (-9)    /* frame of the slot's generation, which is closed    */
 
 #define QF_ABI_VERSION 1
 int qf_abi_version(void);
@@ -920,6 +922,96 @@ int qf_store_append_sel_dev(qf_ctx *ctx, const qf_store_shape *shape, const qf_g
                             const uint8_t *take_dev, uint8_t *store_dev, uint32_t *store_off_dev,
                             uint32_t *store_len_dev, uint16_t *store_index_dev,
                             uint8_t *store_coeffs_dev, uint32_t *store_n_dev, int32_t *status_dev);
+
+/* ---------------------------------------------------------------------------
+ * The generation window.  No reference counterpart.  A stream numbers its
+ * generations without bound in the outer header; every call above counts
+ * generations in slots 0 .. G_src-1.  The window is the persistent map from
+ * wire ids to slots, kept on the device and decided there, in front of
+ * qf_parse_poll_headers_dev: which frames belong to the generation a slot
+ * holds, which slots a newer generation takes over (their state is reset
+ * before the ingest), and which frames are dropped because their generation
+ * is gone (QF_ESTALE) or was delivered (QF_ECLOSED).
+ *
+ * The window state is caller-owned: win_dev holds G_src entries of uint64_t,
+ * 8-byte aligned, zeroed once by the caller (every slot empty).
+ *   entry 0          the slot is empty
+ *   otherwise        bits 0..62 = id + 1, bit 63 = the closed flag
+ * Wire ids are 0 .. 2^62 - 1 (the QUIC varint range); the slot of id x is
+ * x % G_src.  A host may read the entries.  Ids are monotone: there is no
+ * wrap-around arithmetic and no expiry by age.
+ *
+ * One poll of a receiver:
+ *   qf_gen_window_dev          the poll's ids -> frame_gen_dev (the ingest's tags), the evict list
+ *   qf_stream_reset_dev        twice over the evict list, as at the end of a poll
+ *   qf_parse_poll_headers_dev  with frame_gen_dev; a dropped frame (QF_GEN_NONE) gets its QF_EINVAL
+ *   qf_rank_update_sel_batch, qf_store_append_sel_dev, qf_gen_select_dev, qf_decode_frames_sel_dev
+ *   qf_gen_window_sel_dev      over the completed list with QF_WINDOW_CLOSE: the ids that label
+ *                              what is delivered; a later frame of them is QF_ECLOSED
+ *   qf_stream_reset_dev        twice over the completed list
+ * A relay runs qf_recode_frames_sel_dev, reads the ids without closing, and
+ * never closes.
+ * ------------------------------------------------------------------------- */
+#define QF_GEN_NONE 0xFFFFFFFFu
+/* No reference counterpart.  Let N = min(*n_frames_dev, N_max) (n_frames_dev
+ * NULL: N_max), frame_id_dev[f] the wire generation id of frame f, and W the
+ * window before the call.
+ * Newest id per slot.  For each slot s, newest[s] is the largest valid id
+ * among frames f < N with id % G_src == s.  A valid id is < 2^62.  If that id
+ * is larger than the id W[s] holds, or W[s] is empty, the entry becomes
+ * newest[s] + 1, open, with bit 63 clear.  Otherwise the entry is unchanged
+ * byte for byte.  Entries of slots that no frame of the poll maps to are not
+ * written.
+ * Evicted slots.  A slot whose entry was replaced and whose old entry was
+ * non-empty and open is evicted.  The evicted slots are listed ascending in
+ * evict_sel_dev[0..], *n_evict_dev is their number, and evict_id_dev[j], when
+ * given, is the id that was displaced.  Entries at and above *n_evict_dev are
+ * not written.  A displaced closed or empty entry is not listed: its state was
+ * reset when it was closed.  The list is what qf_stream_reset_dev takes as a
+ * qf_gen_sel with n_max = n_evict_max; the caller runs the reset twice, as at
+ * the end of a poll, before the ingest.
+ * Per-frame outputs, for frames f < N (frames at or above N are not written):
+ *   id >= 2^62                                       QF_EINVAL   QF_GEN_NONE
+ *   id equals the id of the updated entry, open      QF_OK       the slot
+ *   id equals the id of the updated entry, closed    QF_ECLOSED  QF_GEN_NONE
+ *   id smaller than the id of the updated entry      QF_ESTALE   QF_GEN_NONE
+ * in frame_status_dev[f] and frame_gen_dev[f].
+ * Newest wins within a poll.  Within one poll the newest id of a slot wins
+ * whatever the arrival order: frames of x and of x + G_src in the same poll
+ * make every frame of x stale.
+ * Determinism.  No output depends on the order of waves or atomics.
+ * Returns QF_EINVAL, before any device work, for a NULL context, G_src == 0 or
+ * G_src > 2^24 (the select's limit), flags != 0, n_evict_max < min(N_max,
+ * G_src) (an eviction needs a frame, so with this bound the list never
+ * overflows and no eviction is lost), a NULL required pointer (win_dev,
+ * evict_sel_dev, n_evict_dev, and the per-frame pointers when N_max > 0), or
+ * win_dev not 8-byte aligned.  N_max == 0 writes *n_evict_dev = 0 and is
+ * QF_OK.
+ * Kernels: a memset of G_src u64 of workspace, k_window_max (a lane per frame,
+ * one atomicMax on id + 1), k_window_apply (a lane per slot), k_gen_select_count
+ * and k_gen_select_scatter over the evicted flags, k_window_tag (a lane per
+ * frame, and lanes for evict_id_dev). */
+int qf_gen_window_dev(qf_ctx *ctx, uint32_t G_src, uint32_t N_max,
+                      const uint64_t *frame_id_dev, const uint32_t *n_frames_dev,
+                      uint64_t *win_dev, uint32_t flags,
+                      uint32_t *frame_gen_dev, int32_t *frame_status_dev,
+                      uint32_t n_evict_max, uint32_t *evict_sel_dev, uint32_t *n_evict_dev,
+                      uint64_t *evict_id_dev);
+
+/* No reference counterpart.  The wire ids of a list, and closing it.  For a
+ * listed entry with sel_dev[j] < G_src and a non-empty window entry,
+ * ids_dev[j] (nullable, n_max entries) is the wire id that slot holds: the
+ * receiver labels what it delivers with it, the relay the frames it emits.
+ * For invalid, unused and empty entries ids_dev[j] = UINT64_MAX.
+ * flags: 0 or QF_WINDOW_CLOSE, which sets bit 63 of the listed non-empty
+ * entries; duplicates are harmless and nothing else is written.  Without the
+ * flag the window is only read.
+ * Returns QF_EINVAL for unknown flag bits, a NULL sel, sel_dev or win_dev,
+ * n_max == 0, G_src == 0, or when there is neither the flag nor ids_dev.
+ * One kernel, k_window_sel, a lane per entry. */
+#define QF_WINDOW_CLOSE 1u
+int qf_gen_window_sel_dev(qf_ctx *ctx, const qf_gen_sel *sel, uint64_t *win_dev,
+                          uint32_t flags, uint64_t *ids_dev);
 
 /* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations

@@ -22,6 +22,8 @@ QF_ERANK = -4
 QF_EDEVICE = -5
 QF_ENOMEM = -6
 QF_ETOOSMALL = -7
+QF_ESTALE = -8
+QF_ECLOSED = -9
 
 _P = ctypes.c_void_p
 _U8 = ctypes.c_uint8
@@ -100,6 +102,8 @@ class GenSel(ctypes.Structure):
 
 
 QF_SELECT_MARK = 1   # qf_gen_select_dev flags: seen[g] = rank[g] for the selected generations
+QF_WINDOW_CLOSE = 1  # qf_gen_window_sel_dev flags: set the closed flag of the listed entries
+QF_GEN_NONE = 0xFFFFFFFF   # qf_gen_window_dev: the tag of a frame that is dropped
 
 
 class RankShape(ctypes.Structure):
@@ -251,6 +255,8 @@ _SIGS = {
                                       _P, _P]),
     "qf_store_append_sel_dev": (_I, [_P, ctypes.POINTER(StoreShape), ctypes.POINTER(GenSel), _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_gen_window_dev": (_I, [_P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _U32, _P, _P, _P]),
+    "qf_gen_window_sel_dev": (_I, [_P, ctypes.POINTER(GenSel), _P, _U32, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

@@ -1144,6 +1144,8 @@ const char* qf_strerror(int s) {
         case QF_EDEVICE: return "HIP device error";
         case QF_ENOMEM: return "out of memory";
         case QF_ETOOSMALL: return "buffer too short";
+        case QF_ESTALE: return "stale frame (its slot holds a newer generation)";
+        case QF_ECLOSED: return "frame of a closed generation";
         default: return "unknown status";
     }
 }

@@ -867,6 +867,47 @@ def store_append_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, s
         _ptr(status)), "store_append_sel")
 
 
+QF_WINDOW_CLOSE = L.QF_WINDOW_CLOSE
+QF_GEN_NONE = L.QF_GEN_NONE
+
+
+def gen_window(frame_id, win, frame_gen, frame_status, evict_sel, n_evict, *, G_src: int, N_max: int,
+               n_evict_max: int, n_frames=None, evict_id=None, ctx: Optional[Context] = None) -> None:
+    """qf_gen_window_dev: the step in front of parse_poll_headers.  frame_id
+    [N_max] u64 wire generation ids, n_frames[0] the frames to look at; win
+    [G_src] u64, the window (0: empty, else id + 1 with bit 63 the closed
+    flag), updated to the newest id per slot.  frame_gen [N_max] receives the
+    ingest's tags (the slot, or QF_GEN_NONE) and frame_status [N_max] QF_OK /
+    QF_ESTALE / QF_ECLOSED / QF_EINVAL; evict_sel [n_evict_max], n_evict[0] and
+    evict_id [n_evict_max] u64 the evicted open slots, ascending, and the ids
+    they held: stream_reset's list."""
+    _need(frame_id, 8 * N_max, "frame_id")
+    _need(n_frames, 4, "n_frames")
+    _need(win, 8 * G_src, "win")
+    _need(frame_gen, 4 * N_max, "frame_gen")
+    _need(frame_status, 4 * N_max, "frame_status")
+    _need(evict_sel, 4 * n_evict_max, "evict_sel")
+    _need(n_evict, 4, "n_evict")
+    _need(evict_id, 8 * n_evict_max, "evict_id")
+    ctx = ctx or default_context()
+    check(L._lib().qf_gen_window_dev(
+        ctx.handle, G_src, N_max, _opt(frame_id), _opt(n_frames), _ptr(win), 0, _opt(frame_gen), _opt(frame_status),
+        n_evict_max, _ptr(evict_sel), _ptr(n_evict), _opt(evict_id)), "gen_window")
+
+
+def gen_window_sel(sel, n_sel, win, *, n_max: int, G_src: int, ids=None, close: bool = False,
+                   ctx: Optional[Context] = None) -> None:
+    """qf_gen_window_sel_dev: ids [n_max] u64 receives the wire id each listed
+    slot holds (UINT64_MAX for invalid, unused and empty entries); close sets
+    the closed flag of the listed non-empty entries of win [G_src] u64."""
+    _need(win, 8 * G_src, "win")
+    _need(ids, 8 * n_max, "ids")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    check(L._lib().qf_gen_window_sel_dev(
+        ctx.handle, ctypes.byref(gs), _ptr(win), QF_WINDOW_CLOSE if close else 0, _opt(ids)), "gen_window_sel")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
