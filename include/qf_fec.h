@@ -1014,6 +1014,80 @@ int qf_gen_window_sel_dev(qf_ctx *ctx, const qf_gen_sel *sel, uint64_t *win_dev,
                           uint32_t flags, uint64_t *ids_dev);
 
 /* ---------------------------------------------------------------------------
+ * Partial decode: what the rows of a generation determine, at any rank.  No
+ * reference counterpart (Decoder::get_decoded_packets returns a full decode
+ * only, decoder.rs:641, 785).  qf_decode_frames_dev answers a generation of
+ * rank < k with QF_ENOTREADY and nothing else; a generation that is displaced
+ * from the slot ring short of rank k, or still short when a stream ends or a
+ * deadline passes, would lose every packet it holds.  These two calls return
+ * every source that the held rows pin down.
+ * Inputs, shape (flags 0), alignment rules, the call-level QF_EINVAL cases and
+ * G == 0 are those of qf_decode_frames_dev; qf_decode_partial_frames_sel_dev
+ * mirrors qf_decode_frames_sel_dev in the same way.
+ * Per generation let
+ *   A = the innovative slots (what qf_rank_batch flags),
+ *   S = the sources with a systematic slot in A,
+ *   c = the number of coded slots in A,
+ *   D = { i not in S : the unit vector e_i lies in the span of the vectors of A }.
+ * Outputs:
+ *   rank_dev, innovative_dev (both nullable)  what qf_rank_batch writes, always
+ *   src_slot_dev[g*k + i] (nullable)  the slot of source i's systematic row for
+ *                       i in S, else 0xFFFF; filled for every generation whose
+ *                       status is QF_OK or QF_ENOTREADY, all 0xFFFF for QF_EINVAL
+ *   n_rec_dev[g]        |D|
+ *   rec_index_dev[g*min(k, r) + m]  the m-th element of D, ascending
+ *   rec_dev             row m = source rec_index[m], exactly L bytes; rows at and
+ *                       above n_rec are not written
+ *   status_dev[g]       QF_OK iff rank == k; QF_ENOTREADY iff rank < k (n == 0
+ *                       included): the outputs above are valid and describe what
+ *                       is known; QF_EINVAL for the row and index rules of
+ *                       qf_decode_frames_dev, for c > min(k, 128) (the control
+ *                       kernel's matrix rows) and for |D| > min(k, r) (the output
+ *                       capacity), each with n_rec 0 and no row written.
+ *                       QF_ERANK is never reported: A is independent.
+ * For a generation of rank k every output byte equals what the mirrored call
+ * writes: D is then the complement of S, ascending in both.  A systematic row
+ * that arrives after coded rows have determined its source is not innovative;
+ * that source is in D and comes through rec_dev, as in the mirrored call.
+ * Listed form: invalid entries get QF_EINVAL, n_rec 0, rank 0, no flags and
+ * src_slot 0xFFFF and nothing is read through them; unused entries get what
+ * the dense call writes for n_rows = 0; duplicates are legal.
+ * Reads:
+ *   - no payload byte of a slot outside A is read;
+ *   - no payload at all is read for a generation with |D| = 0;
+ *   - the payload of a slot of A is not read when its coefficient is zero in
+ *     every determined source: the payload pass is given only the rows that
+ *     some output uses.  A generation displaced with 50 systematic rows and 3
+ *     coded rows that determine nothing costs no row read.
+ * Within a row that is read, the rule of qf_decode_frames_dev holds (aligned
+ * 16-byte units that hold at least one of its bytes).
+ * A call re-reports what it finds each time it runs: a source delivered by an
+ * earlier call over the same rows is reported again.  Remembering what was
+ * already delivered is the caller's business.
+ * Both calls clear qf_ctx_set_payload_stream / qf_ctx_set_payload_wait.
+ * Kernels: k_rank_filter, k_partial_prepare (one wave per generation: the
+ * reduced row echelon form of the c coded rows over the unknown sources, free
+ * columns skipped), then ceil(min(k, r) / 16) passes of k_combine_rows_at; the
+ * listed form runs k_sel_gather first.  No output depends on the order of
+ * waves.
+ * ------------------------------------------------------------------------- */
+int qf_decode_partial_frames_dev(qf_ctx *ctx, const qf_decode_frames_shape *shape, uint32_t G,
+                                 const uint8_t *src_dev, const uint32_t *row_off_dev,
+                                 const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                                 const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                                 uint8_t *rec_dev, uint16_t *rec_index_dev, uint32_t *n_rec_dev,
+                                 int32_t *status_dev, uint32_t *rank_dev, uint8_t *innovative_dev,
+                                 uint16_t *src_slot_dev);
+int qf_decode_partial_frames_sel_dev(qf_ctx *ctx, const qf_decode_frames_shape *shape,
+                                     const qf_gen_sel *sel,
+                                     const uint8_t *src_dev, const uint32_t *row_off_dev,
+                                     const uint32_t *row_len_dev, const uint16_t *row_index_dev,
+                                     const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                                     uint8_t *rec_dev, uint16_t *rec_index_dev, uint32_t *n_rec_dev,
+                                     int32_t *status_dev, uint32_t *rank_dev, uint8_t *innovative_dev,
+                                     uint16_t *src_slot_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations

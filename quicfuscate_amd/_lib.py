@@ -248,6 +248,10 @@ _SIGS = {
                                       _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_recode_frames_sel_dev": (_I, [_P, ctypes.POINTER(RecodeFramesShape), ctypes.POINTER(GenSel), _P, _P, _P, _P,
                                       _P, _P, _P, _U64, _P, _P, _P, _P]),
+    "qf_decode_partial_frames_dev": (_I, [_P, ctypes.POINTER(DecodeFramesShape), _U32, _P, _P, _P, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, _P]),
+    "qf_decode_partial_frames_sel_dev": (_I, [_P, ctypes.POINTER(DecodeFramesShape), ctypes.POINTER(GenSel), _P, _P,
+                                              _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_stream_reset_dev": (_I, [_P, _U32, ctypes.POINTER(GenSel), _P, _P, _P]),
     "qf_parse_poll_headers_dev": (_I, [_P, _U32, _U32, _U32, _P, _U64, _U32, _P, _P, _P, _P, _P, _U32, _U32, _P, _P,
                                        _P, _P, _P, _P, _P, _P, _P, _P]),

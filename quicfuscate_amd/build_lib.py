@@ -31,7 +31,7 @@ LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
            "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip", "qf_select.hip",
-           "qf_poll.hip", "qf_window.hip"]
+           "qf_poll.hip", "qf_window.hip", "qf_partial.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -185,6 +185,9 @@ RESOURCE_RULES = {
     # the generation window's kernels hold one id, one entry and a few
     # addresses per lane: no scratch
     "qf_window.hip": _Rule(("k_window_max", "k_window_apply", "k_window_tag", "k_window_sel"), 4),
+    # the partial decode's control kernel keeps its matrix in LDS and a few
+    # counters per lane: no scratch
+    "qf_partial.hip": _Rule(("k_partial_prepare",), 1, every=True),
 }
 # the sources compiled with resource-usage remarks
 REMARK_SOURCES = ("qf_gf16_bs.hip", *RESOURCE_RULES)

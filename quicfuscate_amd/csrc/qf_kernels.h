@@ -154,6 +154,16 @@ hipError_t launch_combine_slots(const CombineSlotsArgs& a, int PD, int num_cus, 
                                 bool split_ok = true);
 hipError_t launch_decode_prepare(const PrepareArgs& a, hipStream_t st);
 size_t prepare_lds_bytes(uint32_t k, uint32_t e_max, uint32_t max_rows);
+// qf_decode_partial_frames_dev (k_partial_prepare, qf_partial.hip; DESIGN.md
+// 3.18): PrepareArgs with accept and the row_off group required.  The set A is
+// the flagged slots; status is QF_OK at rank k and QF_ENOTREADY below it, and
+// for both n_out / rec_index are the sources outside S that A determines,
+// src_slot the slots of S.  The pair records, bound and min_len are as
+// described there with "recorded" in the place of "accepted": only the slots of
+// A with a nonzero coefficient in some determined source are recorded, and a
+// generation with no determined source, or of another status, records none.
+hipError_t launch_partial_prepare(const PrepareArgs& a, hipStream_t st);
+size_t partial_prepare_lds_bytes(uint32_t k, uint32_t max_rows);
 hipError_t launch_mul_slice(const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n,
                             const uint8_t* explog, int num_cus, hipStream_t st);
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t n, uint64_t seed, uint64_t word_offset,

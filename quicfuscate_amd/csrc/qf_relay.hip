@@ -459,10 +459,13 @@ extern "C" int qf_recode_frames_sel_dev(qf_ctx* ctx, const qf_recode_frames_shap
 // output counts.
 // (sel as in recode_frames_run: the three control and payload kernels of the
 // dense call over the compact arrays, the payload pass reading through the map)
+// partial (qf_decode_partial_frames_dev): k_partial_prepare in
+// the place of k_decode_prepare, over the same arguments and workspace; its
+// records hold the rows some determined source uses, at most the accepted ones.
 static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G, const qf_gen_sel* sel,
                              const uint8_t* src, qf::RowArrays rows, uint8_t* rec, uint16_t* rec_index,
                              uint32_t* n_rec, int32_t* status, uint32_t* rank, uint8_t* innovative,
-                             uint16_t* src_slot) {
+                             uint16_t* src_slot, bool partial = false) {
     qf::ctx_clear_payload_split(ctx);   // as qf_decode_innovative_batch: they apply to qf_decode_batch only
     const uint32_t k = sh->k, r = sh->r, L = sh->L, max_rows = sh->max_rows;
     if (k == 0 || k > 256 || max_rows == 0 || max_rows > 1024 || L == 0 || sh->flags != 0 || sh->reserved != 0)
@@ -475,7 +478,9 @@ static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint
     if (!aligned16(src) || (sh->src_gen_stride & 15) || !aligned16(rec) || (sh->rec_row_stride & 15) ||
         (sh->rec_gen_stride & 15))
         return QF_EINVAL;
-    if (qf::prepare_lds_bytes(k, k < 128 ? k : 128, max_rows) > 160 * 1024) return QF_EINVAL;
+    if ((partial ? qf::partial_prepare_lds_bytes(k, max_rows) : qf::prepare_lds_bytes(k, k < 128 ? k : 128, max_rows)) >
+        160 * 1024)
+        return QF_EINVAL;
     std::unique_lock<std::mutex> lk;
     int s = qf::ctx_lock(ctx, lk);
     if (s) return s;
@@ -517,7 +522,8 @@ static int decode_frames_run(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint
     pa.src_slot = src_slot;
     pa.src_gen_stride = sh->src_gen_stride;
     pa.L = L;
-    QF_PROFILED(ctx, st, "k_decode_prepare", qf::launch_decode_prepare(pa, st));
+    if (partial) QF_PROFILED(ctx, st, "k_partial_prepare", qf::launch_partial_prepare(pa, st));
+    else QF_PROFILED(ctx, st, "k_decode_prepare", qf::launch_decode_prepare(pa, st));
     qf::CombineRowsAtArgs a{};
     a.src = src;
     a.src_gen_stride = sh->src_gen_stride;
@@ -552,4 +558,26 @@ extern "C" int qf_decode_frames_sel_dev(qf_ctx* ctx, const qf_decode_frames_shap
     if (!ctx || !sh || !sel_ok(sel)) return QF_EINVAL;
     return decode_frames_run(ctx, sh, sel->n_max, sel, src, {row_off, row_len, row_index, n_rows, row_coeffs}, rec,
                              rec_index, n_rec, status, rank, innovative, src_slot);
+}
+
+extern "C" int qf_decode_partial_frames_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, uint32_t G,
+                                            const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                                            const uint16_t* row_index, const uint32_t* n_rows,
+                                            const uint8_t* row_coeffs, uint8_t* rec, uint16_t* rec_index,
+                                            uint32_t* n_rec, int32_t* status, uint32_t* rank, uint8_t* innovative,
+                                            uint16_t* src_slot) {
+    if (!ctx || !sh) return QF_EINVAL;
+    return decode_frames_run(ctx, sh, G, nullptr, src, {row_off, row_len, row_index, n_rows, row_coeffs}, rec,
+                             rec_index, n_rec, status, rank, innovative, src_slot, true);
+}
+
+extern "C" int qf_decode_partial_frames_sel_dev(qf_ctx* ctx, const qf_decode_frames_shape* sh, const qf_gen_sel* sel,
+                                                const uint8_t* src, const uint32_t* row_off, const uint32_t* row_len,
+                                                const uint16_t* row_index, const uint32_t* n_rows,
+                                                const uint8_t* row_coeffs, uint8_t* rec, uint16_t* rec_index,
+                                                uint32_t* n_rec, int32_t* status, uint32_t* rank,
+                                                uint8_t* innovative, uint16_t* src_slot) {
+    if (!ctx || !sh || !sel_ok(sel)) return QF_EINVAL;
+    return decode_frames_run(ctx, sh, sel->n_max, sel, src, {row_off, row_len, row_index, n_rows, row_coeffs}, rec,
+                             rec_index, n_rec, status, rank, innovative, src_slot, true);
 }

@@ -587,7 +587,8 @@ def recode_frames(src, row_off, row_len, row_index, row_coeffs, out, out_coeffs,
 
 def decode_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status, k: int, r: int,
                   Lb: int, *, max_rows: int, src_gen_stride: int, rec_row_stride: int, rec_gen_stride: int, G: int,
-                  n_rows=None, rank=None, innovative=None, src_slot=None, ctx: Optional[Context] = None) -> None:
+                  n_rows=None, rank=None, innovative=None, src_slot=None, ctx: Optional[Context] = None,
+                  _call: str = "decode_frames") -> None:
     """qf_decode_frames_dev: decode_innovative_batch over rows that lie where
     they were received (rows as recode_frames': what parse_frame_headers
     leaves, with src = the frames and src_gen_stride = max_rows *
@@ -607,14 +608,25 @@ def decode_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, 
     _need(src_slot, 2 * G * k, "src_slot")
     ctx = ctx or default_context()
     sh = L.DecodeFramesShape(k, r, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride)
-    check(L._lib().qf_decode_frames_dev(
+    check(getattr(L._lib(), f"qf_{_call}_dev")(
         ctx.handle, ctypes.byref(sh), G, _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
         _opt(n_rows), _ptr(row_coeffs),
         _opt(rec), _opt(rec_index),
         _ptr(n_rec), _ptr(status),
         _opt(rank),
         _opt(innovative),
-        _opt(src_slot)), "decode_frames")
+        _opt(src_slot)), _call)
+
+
+def decode_partial_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status, k: int, r: int,
+                          Lb: int, **kw) -> None:
+    """qf_decode_partial_frames_dev: decode_frames' arguments and outputs, for
+    generations of any rank.  n_rec / rec_index / rec: the sources without an
+    accepted systematic row that the accepted rows determine (all of them at
+    rank k, where every output equals decode_frames'); status QF_ENOTREADY
+    below rank k, with those outputs and src_slot valid."""
+    decode_frames(src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status, k, r, Lb,
+                  _call="decode_partial_frames", **kw)
 
 
 def rank_state_bytes(k: int) -> int:
@@ -706,7 +718,7 @@ def _gen_sel(sel, n_sel, n_max: int, G_src: int) -> "L.GenSel":
 def decode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status,
                       k: int, r: int, Lb: int, *, n_max: int, G_src: int, max_rows: int, src_gen_stride: int,
                       rec_row_stride: int, rec_gen_stride: int, n_rows=None, rank=None, innovative=None,
-                      src_slot=None, ctx: Optional[Context] = None) -> None:
+                      src_slot=None, ctx: Optional[Context] = None, _call: str = "decode_frames_sel") -> None:
     """qf_decode_frames_sel_dev: decode_frames over the generations sel[0 ..
     min(n_sel[0], n_max)) (n_sel None: n_max) of source arrays that hold G_src
     generations.  Every output is compact: entry j of rec, rec_index, n_rec,
@@ -725,14 +737,23 @@ def decode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, 
     gs = _gen_sel(sel, n_sel, n_max, G_src)
     ctx = ctx or default_context()
     sh = L.DecodeFramesShape(k, r, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride)
-    check(L._lib().qf_decode_frames_sel_dev(
+    check(getattr(L._lib(), f"qf_{_call}_dev")(
         ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _ptr(src), _ptr(row_off), _ptr(row_len), _ptr(row_index),
         _opt(n_rows), _ptr(row_coeffs),
         _opt(rec), _opt(rec_index),
         _ptr(n_rec), _ptr(status),
         _opt(rank),
         _opt(innovative),
-        _opt(src_slot)), "decode_frames_sel")
+        _opt(src_slot)), _call)
+
+
+def decode_partial_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec,
+                              status, k: int, r: int, Lb: int, **kw) -> None:
+    """qf_decode_partial_frames_sel_dev: decode_partial_frames over a list, with
+    decode_frames_sel's arguments and compact outputs (the evict list of
+    gen_window before the resets, or gen_select with min_rank 1 for a flush)."""
+    decode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, rec, rec_index, n_rec, status, k, r,
+                      Lb, _call="decode_partial_frames_sel", **kw)
 
 
 def recode_frames_sel(sel, n_sel, src, row_off, row_len, row_index, row_coeffs, out, out_coeffs, status, k: int,
