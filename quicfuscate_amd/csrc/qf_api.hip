@@ -1106,25 +1106,6 @@ hipEvent_t ctx_prof_begin(qf_ctx* ctx, hipStream_t st) { return prof_begin(ctx, 
 void ctx_prof_end(qf_ctx* ctx, hipStream_t st, hipEvent_t ev, const std::string& name) {
     prof_end(ctx, st, ev, name);
 }
-
-hipError_t launch_frame_batch(const uint8_t* src, const uint8_t* rep, const qf_encode_shape& sh, uint32_t G,
-                              uint8_t* frames, uint64_t frame_stride, uint32_t* frame_len,
-                              const uint8_t* explog, int num_cus, hipStream_t st);
-hipError_t launch_parse_frames(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
-                               const uint64_t* ids, const uint32_t* n_frames, uint32_t k, uint32_t r, uint32_t L,
-                               uint32_t G, uint32_t max_rows, uint8_t* rows, uint64_t row_stride,
-                               uint64_t rows_gen_stride, uint16_t* row_index, uint32_t* n_rows,
-                               int32_t* frame_status, const uint8_t* explog, hipStream_t st);
-hipError_t launch_frame_rows(const uint8_t* rows, const uint16_t* row_index, const uint32_t* n_rows,
-                             const uint8_t* row_coeffs, const uint32_t* row_len, const qf_frame_rows_shape& sh,
-                             uint32_t G, uint8_t* frames, uint32_t* frame_len, uint32_t* frame_off,
-                             const uint8_t* explog, int num_cus, hipStream_t st);
-hipError_t launch_parse_frames_coded(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
-                                     const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
-                                     uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint8_t* rows,
-                                     uint64_t row_stride, uint64_t rows_gen_stride, uint16_t* row_index,
-                                     uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len,
-                                     int32_t* frame_status, hipStream_t st);
 }  // namespace qf
 
 extern "C" {
@@ -1751,9 +1732,21 @@ int qf_frame_batch_dev(qf_ctx* ctx, const qf_encode_shape* sh, uint32_t G, const
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    QF_PROFILED(ctx, ctx->stream, "k_frame_batch",
-                qf::launch_frame_batch(src, rep, *sh, G, frames, frame_stride, frame_len, ctx->d_explog,
-                                       ctx->num_cus, ctx->stream));
+    qf::FrameArgs a{};
+    a.src = src;
+    a.rep = rep;
+    a.src_row_stride = sh->src_row_stride;
+    a.src_gen_stride = sh->src_gen_stride;
+    a.rep_row_stride = sh->rep_row_stride;
+    a.rep_gen_stride = sh->rep_gen_stride;
+    a.frames = frames;
+    a.frame_stride = frame_stride;
+    a.frame_len = frame_len;
+    a.explog = ctx->d_explog;
+    a.k = k;
+    a.r = r;
+    a.L = L;
+    QF_PROFILED(ctx, ctx->stream, "k_frame_batch", qf::launch_frame_batch(a, G, ctx->num_cus, ctx->stream));
     return QF_OK;
 }
 
@@ -1772,10 +1765,24 @@ int qf_parse_frames_dev(qf_ctx* ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    QF_PROFILED(ctx, ctx->stream, "k_parse_frames",
-                qf::launch_parse_frames(frames, frame_stride, frame_len, ids, n_frames, k, r, L, G, max_rows, rows,
-                                        row_stride, rows_gen_stride, row_index, n_rows, frame_status,
-                                        ctx->d_explog, ctx->stream));
+    qf::ParseArgs a{};
+    a.frames = frames;
+    a.frame_stride = frame_stride;
+    a.frame_len = frame_len;
+    a.ids = ids;
+    a.n_frames = n_frames;
+    a.rows = rows;
+    a.row_stride = row_stride;
+    a.rows_gen_stride = rows_gen_stride;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.frame_status = frame_status;
+    a.explog = ctx->d_explog;
+    a.k = k;
+    a.r = r;
+    a.L = L;
+    a.max_rows = max_rows;
+    QF_PROFILED(ctx, ctx->stream, "k_parse_frames", qf::launch_parse_frames(a, G, ctx->stream));
     return QF_OK;
 }
 
@@ -1800,9 +1807,24 @@ int qf_frame_rows_dev(qf_ctx* ctx, const qf_frame_rows_shape* sh, uint32_t G, co
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    QF_PROFILED(ctx, ctx->stream, "k_frame_rows",
-                qf::launch_frame_rows(in_place ? nullptr : rows, row_index, n_rows, row_coeffs, row_len, *sh, G,
-                                      frames, frame_len, frame_off, ctx->d_explog, ctx->num_cus, ctx->stream));
+    qf::FrameRowsArgs a{};
+    a.rows = in_place ? nullptr : rows;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.row_coeffs = row_coeffs;
+    a.row_len = row_len;
+    a.frames = frames;
+    a.frame_len = frame_len;
+    a.frame_off = frame_off;
+    a.explog = ctx->d_explog;
+    a.row_stride = sh->row_stride;
+    a.rows_gen_stride = sh->rows_gen_stride;
+    a.frame_stride = sh->frame_stride;
+    a.k = k;
+    a.r = r;
+    a.L = L;
+    a.max_rows = sh->max_rows;
+    QF_PROFILED(ctx, ctx->stream, "k_frame_rows", qf::launch_frame_rows(a, G, ctx->num_cus, ctx->stream));
     return QF_OK;
 }
 
@@ -1823,10 +1845,25 @@ int qf_parse_frames_coded_dev(qf_ctx* ctx, uint32_t k, uint32_t L, uint32_t G, u
     std::lock_guard<std::mutex> g(ctx->mu);
     int s = ensure_device(ctx);
     if (s) return s;
-    QF_PROFILED(ctx, ctx->stream, "k_parse_frames_coded",
-                qf::launch_parse_frames_coded(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
-                                              max_rows, rows, row_stride, rows_gen_stride, row_index, n_rows,
-                                              row_coeffs, row_len, frame_status, ctx->stream));
+    qf::ParseCodedArgs a{};
+    a.frames = frames;
+    a.frame_stride = frame_stride;
+    a.frame_len = frame_len;
+    a.frame_off = frame_off;
+    a.ids = ids;
+    a.n_frames = n_frames;
+    a.rows = rows;
+    a.row_stride = row_stride;
+    a.rows_gen_stride = rows_gen_stride;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.row_coeffs = row_coeffs;
+    a.row_len = row_len;
+    a.frame_status = frame_status;
+    a.k = k;
+    a.L = L;
+    a.max_rows = max_rows;
+    QF_PROFILED(ctx, ctx->stream, "k_parse_frames_coded", qf::launch_parse_frames_coded(a, G, ctx->stream));
     return QF_OK;
 }
 

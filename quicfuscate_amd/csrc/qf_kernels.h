@@ -407,4 +407,96 @@ hipError_t launch_encode_small(const EncodeSmallArgs& a, int num_cus, hipStream_
 // 64-unit tile per block (send batches of many windows).
 hipError_t launch_encode_windows(const EncodeSmallArgs& a, int num_cus, hipStream_t st);
 
+// Wire framing (qf_wire.hip).  The callers fill the fields by name; the
+// launchers derive the grid and the fields marked "derived" from them and G,
+// and launch nothing for an empty batch.
+// k_frame_batch: an encode batch's sources and Cauchy repairs -> frames.
+struct FrameArgs {
+    const uint8_t* src;
+    const uint8_t* rep;
+    uint64_t src_row_stride, src_gen_stride, rep_row_stride, rep_gen_stride;
+    uint8_t* frames;
+    uint64_t frame_stride;
+    uint32_t* frame_len;
+    const uint8_t* explog;
+    uint32_t k, r, L;
+    uint32_t blocks_per_frame;  // derived: ceil((3 + k + L) / 16)
+    uint64_t total_blocks;      // derived
+};
+hipError_t launch_frame_batch(const FrameArgs& a, uint32_t G, int num_cus, hipStream_t st);
+
+// k_parse_frames: received frames of the Cauchy code -> decode-batch rows.
+struct ParseArgs {
+    const uint8_t* frames;
+    uint64_t frame_stride;
+    const uint32_t* frame_len;
+    const uint64_t* ids;
+    const uint32_t* n_frames;
+    uint8_t* rows;
+    uint64_t row_stride, rows_gen_stride;
+    uint16_t* row_index;
+    uint32_t* n_rows;
+    int32_t* frame_status;
+    const uint8_t* explog;
+    uint32_t k, r, L, max_rows;
+};
+hipError_t launch_parse_frames(const ParseArgs& a, uint32_t G, hipStream_t st);
+
+// k_frame_rows: rows with index and vector -> frames in payload-aligned slots.
+struct FrameRowsArgs {
+    const uint8_t* rows;        // NULL in place
+    const uint16_t* row_index;  // NULL: every row coded
+    const uint32_t* n_rows;     // NULL: max_rows
+    const uint8_t* row_coeffs;  // NULL: Cauchy rows of (k, r)
+    const uint32_t* row_len;    // NULL: L
+    uint8_t* frames;
+    uint32_t* frame_len;
+    uint32_t* frame_off;        // may be NULL
+    const uint8_t* explog;
+    uint64_t row_stride, rows_gen_stride, frame_stride;
+    uint32_t k, r, L, max_rows;
+    uint32_t P;                 // derived: qf_frame_payload_offset(k)
+    uint32_t hdr_blocks;        // derived: P / 16
+    uint32_t blocks_per_frame;  // derived: hdr_blocks (+ ceil(L / 16) in copy mode)
+    uint64_t total_blocks;      // derived
+};
+hipError_t launch_frame_rows(const FrameRowsArgs& a, uint32_t G, int num_cus, hipStream_t st);
+
+// k_parse_frames_coded: frames at an offset in their slots -> rows, any vector.
+struct ParseCodedArgs {
+    const uint8_t* frames;
+    uint64_t frame_stride;
+    const uint32_t* frame_len;
+    const uint32_t* frame_off;  // NULL: 0
+    const uint64_t* ids;
+    const uint32_t* n_frames;
+    uint8_t* rows;
+    uint64_t row_stride, rows_gen_stride;
+    uint16_t* row_index;
+    uint32_t* n_rows;
+    uint8_t* row_coeffs;
+    uint32_t* row_len;          // may be NULL
+    int32_t* frame_status;
+    uint32_t k, L, max_rows;
+};
+hipError_t launch_parse_frames_coded(const ParseCodedArgs& a, uint32_t G, hipStream_t st);
+
+// k_parse_frame_headers: the same decisions, the payloads left where they are.
+struct ParseHeadersArgs {
+    const uint8_t* frames;
+    uint64_t frame_stride;
+    const uint32_t* frame_len;
+    const uint32_t* frame_off;  // NULL: 0
+    const uint64_t* ids;
+    const uint32_t* n_frames;
+    uint16_t* row_index;
+    uint32_t* n_rows;
+    uint8_t* row_coeffs;
+    uint32_t* row_len;
+    uint32_t* row_off;
+    int32_t* frame_status;
+    uint32_t k, L, max_rows;
+};
+hipError_t launch_parse_frame_headers(const ParseHeadersArgs& a, uint32_t G, hipStream_t st);
+
 }  // namespace qf

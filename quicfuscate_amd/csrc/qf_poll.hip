@@ -20,16 +20,16 @@
 //                  k_parse_frame_headers' decisions (qf_wire.hip) in that
 //                  order, 64 frames at a time: status, ballot-prefix
 //                  compaction, vector copy, the unit vector of a systematic
-//                  frame.  The decision and the copy are duplicated here, so
-//                  that kernel stays as it is.
+//                  frame.  The decision and the copy are the ones that
+//                  kernel calls (frame_head and vector_block, qf_wire_dev.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mutex>
 
 #include "qf_fec.h"
-#include "qf_gf_dev.h"
 #include "qf_internal.h"
+#include "qf_wire_dev.h"
 
 namespace qf {
 
@@ -112,31 +112,6 @@ __global__ void __launch_bounds__(256) k_poll_place(PollPlaceArgs a) {
     if (slot < a.max_rows) a.place[(uint64_t)lo * a.max_rows + slot] = f;   // (always: the count is the claims)
 }
 
-// bytes [off, off + 4) of a buffer read through aligned dwords
-QF_DEV uint32_t poll_load_u32(const uint8_t* base, uint64_t off) {
-    const uint64_t al = off & ~3ull;
-    const uint32_t sh = (uint32_t)(off & 3) * 8;
-    const uint32_t lo = *reinterpret_cast<const uint32_t*>(base + al);
-    if (sh == 0) return lo;
-    const uint32_t hi = *reinterpret_cast<const uint32_t*>(base + al + 4);
-    return __builtin_amdgcn_alignbit(hi, lo, sh);
-}
-
-// 16 bytes from slot byte o of a frame whose readable bytes end at slot byte
-// `end` (qf_wire.hip's rule: an aligned 16-byte load, else aligned dwords,
-// which touch up to 3 bytes past o + 16)
-QF_DEV bool poll_can_copy16(uint32_t o, uint32_t end) { return (o & 15) == 0 ? o + 16 <= end : o + 20 <= end; }
-
-QF_DEV uint4 poll_load16(const uint8_t* slot, uint32_t o) {
-    if ((o & 15) == 0) return *reinterpret_cast<const uint4*>(slot + o);
-    uint4 v;
-    v.x = poll_load_u32(slot, o);
-    v.y = poll_load_u32(slot, o + 4);
-    v.z = poll_load_u32(slot, o + 8);
-    v.w = poll_load_u32(slot, o + 12);
-    return v;
-}
-
 __global__ void __launch_bounds__(64) k_poll_headers(PollHeadersArgs a) {
     __shared__ uint32_t raw[1024];     // the entry's frame numbers as claimed
     __shared__ uint32_t srt[1024];     // ... ascending: the arrival order
@@ -182,55 +157,30 @@ __global__ void __launch_bounds__(64) k_poll_headers(PollHeadersArgs a) {
     uint32_t base = 0;
     for (uint32_t s0 = 0; s0 < c; s0 += 64) {   // c <= 1024: 16 chunks at most
         const uint32_t s = s0 + lane;
-        int32_t st = QF_OK;
-        uint32_t idx = 0xFFFF, pay = 0, plen = 0, f = 0;
+        FrameHead h{QF_OK, 0xFFFF, 0, 0};
+        uint32_t f = 0;
         bool in = s < c;
         if (in) {
             f = srt[s];
             in = f < N;   // (always)
         }
         if (in) {
-            const uint32_t flen = a.frame_len[f];
-            const uint32_t foff = a.frame_off ? a.frame_off[f] : 0;
-            uint32_t off = 0;
-            if (flen == 0 || (uint64_t)foff + flen > a.frame_stride) {
-                st = QF_EINVAL;  // "Raw data is empty", or not inside its slot
-            } else {
-                const uint8_t* fr = a.frames + (uint64_t)f * a.frame_stride + foff;
-                if (fr[0] == 1) {
-                    off = 1;
-                    idx = (uint32_t)(a.ids[f] % a.k);  // decoder.rs:684
-                } else if (flen < 3) {
-                    st = QF_ETOOSMALL;  // coefficient length missing (encoder.rs:33-38)
-                } else {
-                    const uint32_t cl = ((uint32_t)fr[1] << 8) | fr[2];
-                    if (flen < 3 + cl) st = QF_ETOOSMALL;  // coefficients truncated
-                    else if (cl != a.k) st = QF_ERANGE;
-                    off = 3 + cl;
-                    idx = a.k;
-                }
-            }
-            if (st == QF_OK) {
-                plen = flen - off;
-                pay = foff + off;
-                // a payload that cannot be read in place: longer than L, or not
-                // at a multiple of 16 in its slot
-                if (plen > a.L || (pay & 15)) st = QF_EINVAL;
-            }
-            a.frame_status[f] = st;
+            h = frame_head(a.frames + (uint64_t)f * a.frame_stride, a.frame_len[f], a.frame_off ? a.frame_off[f] : 0,
+                           a.frame_stride, a.ids + f, a.k, a.L, true);
+            a.frame_status[f] = h.st;
         }
-        const bool ok = in && st == QF_OK;
+        const bool ok = in && h.st == QF_OK;
         const uint64_t bal = __ballot(ok);
         const uint32_t before = (uint32_t)__popcll(bal & lt_mask);
         const uint32_t cnt = (uint32_t)__popcll(bal);
         if (ok) {
             const uint64_t o = out0 + base + before;   // base + cnt <= c <= max_rows
-            a.row_index[o] = (uint16_t)idx;
-            a.row_len[o] = plen;
-            a.row_off[o] = (uint32_t)((uint64_t)f * a.frame_stride) + pay;   // N_max * frame_stride <= 2^32
+            a.row_index[o] = (uint16_t)h.idx;
+            a.row_len[o] = h.plen;
+            a.row_off[o] = (uint32_t)((uint64_t)f * a.frame_stride) + h.pay;   // N_max * frame_stride <= 2^32
             of_frame[before] = f;
-            of_pay[before] = pay;
-            of_idx[before] = idx;
+            of_pay[before] = h.pay;
+            of_idx[before] = h.idx;
         }
         __syncthreads();
         // 16-byte blocks of the accepted rows' coefficient vectors (the unit
@@ -238,36 +188,8 @@ __global__ void __launch_bounds__(64) k_poll_headers(PollHeadersArgs a) {
         for (uint32_t w = lane; w < cnt * cpr; w += 64) {
             const uint32_t i = w / cpr, u = w - i * cpr;
             const uint8_t* fslot = a.frames + (uint64_t)of_frame[i] * a.frame_stride;
-            const uint32_t pay_i = of_pay[i], idx_i = of_idx[i];
-            const uint32_t c0 = u * 16;
-            const uint32_t cend = min(c0 + 16, a.k);
-            uint8_t* cd = a.row_coeffs + (out0 + base + i) * a.k;
-            const bool wide = c0 + 16 <= a.k && ((uintptr_t)(cd + c0) & 15) == 0;
-            if (idx_i < a.k) {
-                if (wide) {
-                    uint4 v = make_uint4(0, 0, 0, 0);
-                    if (idx_i >= c0 && idx_i < c0 + 16) {
-                        const uint32_t bit = 1u << (8 * (idx_i & 3));
-                        const uint32_t q = (idx_i - c0) >> 2;
-                        v.x = q == 0 ? bit : 0;
-                        v.y = q == 1 ? bit : 0;
-                        v.z = q == 2 ? bit : 0;
-                        v.w = q == 3 ? bit : 0;
-                    }
-                    *reinterpret_cast<uint4*>(cd + c0) = v;
-                } else {
-                    for (uint32_t t = c0; t < cend; ++t) cd[t] = t == idx_i ? 1 : 0;
-                }
-                continue;
-            }
-            // the vector sits in front of the payload: bytes [pay - k, pay) of the
-            // slot; the readable bytes end with it (no payload byte is touched)
-            const uint32_t v0 = pay_i - a.k;
-            if (wide && poll_can_copy16(v0 + c0, pay_i)) {
-                *reinterpret_cast<uint4*>(cd + c0) = poll_load16(fslot, v0 + c0);
-            } else {
-                for (uint32_t t = c0; t < cend; ++t) cd[t] = fslot[v0 + t];
-            }
+            // the readable bytes end with the vector (no payload byte is touched)
+            vector_block(a.row_coeffs + (out0 + base + i) * a.k, u * 16, a.k, of_idx[i], fslot, of_pay[i], of_pay[i]);
         }
         __syncthreads();
         base += cnt;

@@ -240,12 +240,6 @@ hipError_t launch_combine_rows_at(const CombineRowsAtArgs& a, int num_cus, hipSt
     return hipSuccess;
 }
 
-hipError_t launch_parse_frame_headers(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
-                                      const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
-                                      uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint16_t* row_index,
-                                      uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len, uint32_t* row_off,
-                                      int32_t* frame_status, hipStream_t st);   // qf_wire.hip
-
 }  // namespace qf
 
 extern "C" int qf_parse_frame_headers_dev(qf_ctx* ctx, uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows,
@@ -266,10 +260,23 @@ extern "C" int qf_parse_frame_headers_dev(qf_ctx* ctx, uint32_t k, uint32_t L, u
     int s = qf::ctx_lock(ctx, lk);
     if (s) return s;
     hipStream_t st = qf::ctx_stream(ctx);
-    QF_PROFILED(ctx, st, "k_parse_frame_headers",
-                qf::launch_parse_frame_headers(frames, frame_stride, frame_len, frame_off, ids, n_frames, k, L, G,
-                                               max_rows, row_index, n_rows, row_coeffs, row_len, row_off,
-                                               frame_status, st));
+    qf::ParseHeadersArgs a{};
+    a.frames = frames;
+    a.frame_stride = frame_stride;
+    a.frame_len = frame_len;
+    a.frame_off = frame_off;
+    a.ids = ids;
+    a.n_frames = n_frames;
+    a.row_index = row_index;
+    a.n_rows = n_rows;
+    a.row_coeffs = row_coeffs;
+    a.row_len = row_len;
+    a.row_off = row_off;
+    a.frame_status = frame_status;
+    a.k = k;
+    a.L = L;
+    a.max_rows = max_rows;
+    QF_PROFILED(ctx, st, "k_parse_frame_headers", qf::launch_parse_frame_headers(a, G, st));
     return QF_OK;
 }
 

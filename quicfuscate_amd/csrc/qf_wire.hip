@@ -14,40 +14,24 @@
 // Payloads sit at byte offset 1 or 3 + k inside a frame, so the copy loops
 // move 16-byte blocks assembled from aligned dwords with v_alignbit (one
 // block per lane); the header bytes and the ragged tail go byte by byte.
+// The loads, the header decision, the coefficient-vector block and the
+// compaction prefix of the parsers are qf_wire_dev.h's, shared with
+// k_poll_headers (qf_poll.hip); the argument structs are qf_kernels.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "qf_fec.h"
-#include "qf_gf_dev.h"
+#include "qf_kernels.h"
+#include "qf_wire_dev.h"
+
+namespace qf {
 
 namespace {
-
-// bytes [off, off + 4) of a buffer read through aligned dwords
-QF_DEV uint32_t load_u32_unaligned(const uint8_t* base, uint64_t off) {
-    const uint64_t a = off & ~3ull;
-    const uint32_t sh = (uint32_t)(off & 3) * 8;
-    const uint32_t lo = *reinterpret_cast<const uint32_t*>(base + a);
-    if (sh == 0) return lo;
-    const uint32_t hi = *reinterpret_cast<const uint32_t*>(base + a + 4);
-    return __builtin_amdgcn_alignbit(hi, lo, sh);
-}
 
 QF_DEV uint8_t cauchy_coeff(const uint8_t* sexp, const uint8_t* slog, uint32_t i, uint32_t k, uint32_t j) {
     const uint32_t d = (i & 0xFF) ^ ((k + j) & 0xFF);  // decoder.rs:280-298 (k + r <= 256: d != 0)
     return sexp[255 - slog[d]];
 }
-
-struct FrameArgs {
-    const uint8_t* src;
-    const uint8_t* rep;
-    uint64_t src_row_stride, src_gen_stride, rep_row_stride, rep_gen_stride;
-    uint8_t* frames;
-    uint64_t frame_stride;
-    uint32_t* frame_len;
-    const uint8_t* explog;
-    uint32_t k, r, L, blocks_per_frame;
-    uint64_t total_blocks;
-};
 
 // one lane per 16-byte block of a frame (frames are frame_stride apart)
 __global__ void __launch_bounds__(256) k_frame_batch(FrameArgs a) {
@@ -95,21 +79,6 @@ __global__ void __launch_bounds__(256) k_frame_batch(FrameArgs a) {
         }
     }
 }
-
-struct ParseArgs {
-    const uint8_t* frames;
-    uint64_t frame_stride;
-    const uint32_t* frame_len;
-    const uint64_t* ids;
-    const uint32_t* n_frames;
-    uint8_t* rows;
-    uint64_t row_stride, rows_gen_stride;
-    uint16_t* row_index;
-    uint32_t* n_rows;
-    int32_t* frame_status;
-    const uint8_t* explog;
-    uint32_t k, r, L, max_rows;
-};
 
 // one 256-thread block per generation
 __global__ void __launch_bounds__(256) k_parse_frames(ParseArgs a) {
@@ -167,22 +136,14 @@ __global__ void __launch_bounds__(256) k_parse_frames(ParseArgs a) {
             a.frame_status[fi] = st;
         }
         const bool ok = s < nf && st == QF_OK;
-        // block-wide exclusive prefix of ok (4 waves)
-        const uint64_t bal = __ballot(ok);
-        const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        const uint32_t before = __popcll(bal & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
-        if (lane == 0) wave_cnt[w] = __popcll(bal);
-        __syncthreads();
-        uint32_t woff = 0;
-        for (uint32_t q = 0; q < w; ++q) woff += wave_cnt[q];
-        uint32_t total = 0;
-        for (uint32_t q = 0; q < 4; ++q) total += wave_cnt[q];
+        uint32_t total;
+        const uint32_t slot = base + block_prefix4(ok, wave_cnt, total);
         if (s < nf && s < 1024) {
-            slot_of[s] = ok ? base + woff + before : 0xFFFFFFFFu;
+            slot_of[s] = ok ? slot : 0xFFFFFFFFu;
             off_of[s] = off;
             len_of[s] = plen;
         }
-        if (ok) a.row_index[(uint64_t)g * a.max_rows + base + woff + before] = (uint16_t)idx;
+        if (ok) a.row_index[(uint64_t)g * a.max_rows + slot] = (uint16_t)idx;
         base += total;
         __syncthreads();
     }
@@ -219,41 +180,6 @@ __global__ void __launch_bounds__(256) k_parse_frames(ParseArgs a) {
 // byte P = round_up(3 + k, 16) of its slot and the frame's header directly in
 // front of it, so payload copies are aligned 16-byte loads and stores.
 // ---------------------------------------------------------------------------
-
-// 16 bytes from slot byte o (any alignment) of a frame whose readable bytes end
-// at slot byte `end`: one aligned 16-byte load, else aligned dwords joined with
-// v_alignbit (which touch up to 3 bytes past o + 16, hence the 20).  The
-// caller has checked can_copy16(o, end).
-QF_DEV bool can_copy16(uint32_t o, uint32_t end) {
-    return (o & 15) == 0 ? o + 16 <= end : o + 20 <= end;
-}
-
-QF_DEV uint4 load16(const uint8_t* slot, uint32_t o) {
-    if ((o & 15) == 0) return *reinterpret_cast<const uint4*>(slot + o);
-    uint4 v;
-    v.x = load_u32_unaligned(slot, o);
-    v.y = load_u32_unaligned(slot, o + 4);
-    v.z = load_u32_unaligned(slot, o + 8);
-    v.w = load_u32_unaligned(slot, o + 12);
-    return v;
-}
-
-struct FrameRowsArgs {
-    const uint8_t* rows;        // NULL in place
-    const uint16_t* row_index;  // NULL: every row coded
-    const uint32_t* n_rows;     // NULL: max_rows
-    const uint8_t* row_coeffs;  // NULL: Cauchy rows of (k, r)
-    const uint32_t* row_len;    // NULL: L
-    uint8_t* frames;
-    uint32_t* frame_len;
-    uint32_t* frame_off;        // may be NULL
-    const uint8_t* explog;
-    uint64_t row_stride, rows_gen_stride, frame_stride;
-    uint32_t k, r, L, max_rows, P;
-    uint32_t hdr_blocks;        // P / 16
-    uint32_t blocks_per_frame;  // hdr_blocks (+ ceil(L / 16) in copy mode)
-    uint64_t total_blocks;
-};
 
 // one lane per 16-byte block of a slot: blocks [0, P/16) hold the header,
 // the blocks behind them the payload (copy mode only)
@@ -323,23 +249,6 @@ __global__ void __launch_bounds__(256) k_frame_rows(FrameRowsArgs a) {
     }
 }
 
-struct ParseCodedArgs {
-    const uint8_t* frames;
-    uint64_t frame_stride;
-    const uint32_t* frame_len;
-    const uint32_t* frame_off;  // NULL: 0
-    const uint64_t* ids;
-    const uint32_t* n_frames;
-    uint8_t* rows;
-    uint64_t row_stride, rows_gen_stride;
-    uint16_t* row_index;
-    uint32_t* n_rows;
-    uint8_t* row_coeffs;
-    uint32_t* row_len;          // may be NULL
-    int32_t* frame_status;
-    uint32_t k, L, max_rows;
-};
-
 // one 256-thread block per generation; k_parse_frames with any coefficient
 // vector accepted and written out, and frames at an offset inside their slots
 __global__ void __launch_bounds__(256) k_parse_frames_coded(ParseCodedArgs a) {
@@ -353,56 +262,26 @@ __global__ void __launch_bounds__(256) k_parse_frames_coded(ParseCodedArgs a) {
     uint32_t base = 0;
     for (uint32_t s0 = 0; s0 < nf; s0 += blockDim.x) {
         const uint32_t s = s0 + threadIdx.x;
-        int32_t st = QF_OK;
-        uint32_t idx = 0xFFFF, pay = 0, plen = 0;
+        FrameHead h{QF_OK, 0xFFFF, 0, 0};
         if (s < nf) {
             const uint64_t fi = (uint64_t)g * a.max_rows + s;
-            const uint32_t flen = a.frame_len[fi];
-            const uint32_t foff = a.frame_off ? a.frame_off[fi] : 0;
-            const uint8_t* fr = a.frames + fi * a.frame_stride + foff;
-            uint32_t off = 0;
-            if (flen == 0 || (uint64_t)foff + flen > a.frame_stride) {
-                st = QF_EINVAL;  // "Raw data is empty", or not inside its slot
-            } else if (fr[0] == 1) {
-                off = 1;
-                idx = (uint32_t)(a.ids[fi] % a.k);  // decoder.rs:684
-            } else if (flen < 3) {
-                st = QF_ETOOSMALL;  // coefficient length missing (encoder.rs:33-38)
-            } else {
-                const uint32_t cl = ((uint32_t)fr[1] << 8) | fr[2];
-                if (flen < 3 + cl) st = QF_ETOOSMALL;  // coefficients truncated
-                else if (cl != a.k) st = QF_ERANGE;
-                off = 3 + cl;
-                idx = a.k;
-            }
-            if (st == QF_OK) {
-                plen = flen - off;
-                pay = foff + off;
-                if (plen > a.L) st = QF_EINVAL;
-            }
-            a.frame_status[fi] = st;
+            h = frame_head(a.frames + fi * a.frame_stride, a.frame_len[fi], a.frame_off ? a.frame_off[fi] : 0,
+                           a.frame_stride, a.ids + fi, a.k, a.L, false);
+            a.frame_status[fi] = h.st;
         }
-        const bool ok = s < nf && st == QF_OK;
-        // block-wide exclusive prefix of ok (4 waves)
-        const uint64_t bal = __ballot(ok);
-        const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        const uint32_t before = __popcll(bal & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
-        if (lane == 0) wave_cnt[w] = __popcll(bal);
-        __syncthreads();
-        uint32_t woff = 0;
-        for (uint32_t q = 0; q < w; ++q) woff += wave_cnt[q];
-        uint32_t total = 0;
-        for (uint32_t q = 0; q < 4; ++q) total += wave_cnt[q];
+        const bool ok = s < nf && h.st == QF_OK;
+        uint32_t total;
+        const uint32_t slot = base + block_prefix4(ok, wave_cnt, total);
         if (s < nf) {   // nf <= max_rows <= 1024
-            slot_of[s] = ok ? base + woff + before : 0xFFFFFFFFu;
-            pay_of[s] = pay;
-            len_of[s] = plen;
-            idx_of[s] = (uint16_t)idx;
+            slot_of[s] = ok ? slot : 0xFFFFFFFFu;
+            pay_of[s] = h.pay;
+            len_of[s] = h.plen;
+            idx_of[s] = (uint16_t)h.idx;
         }
         if (ok) {
-            const uint64_t o = (uint64_t)g * a.max_rows + base + woff + before;
-            a.row_index[o] = (uint16_t)idx;
-            if (a.row_len) a.row_len[o] = plen;
+            const uint64_t o = (uint64_t)g * a.max_rows + slot;
+            a.row_index[o] = (uint16_t)h.idx;
+            if (a.row_len) a.row_len[o] = h.plen;
         }
         base += total;
         __syncthreads();
@@ -433,52 +312,14 @@ __global__ void __launch_bounds__(256) k_parse_frames_coded(ParseCodedArgs a) {
             continue;
         }
         const uint32_t c0 = (u - bpr) * 16;
-        const uint32_t cend = min(c0 + 16, a.k);
         uint8_t* cd = a.row_coeffs + ((uint64_t)g * a.max_rows + slot) * a.k;
         const uint32_t idx = idx_of[s];
-        const bool wide = c0 + 16 <= a.k && ((uintptr_t)(cd + c0) & 15) == 0;
-        if (idx < a.k) {
-            if (wide) {
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (idx >= c0 && idx < c0 + 16) {
-                    const uint32_t bit = 1u << (8 * (idx & 3));
-                    const uint32_t q = (idx - c0) >> 2;
-                    v.x = q == 0 ? bit : 0;
-                    v.y = q == 1 ? bit : 0;
-                    v.z = q == 2 ? bit : 0;
-                    v.w = q == 3 ? bit : 0;
-                }
-                *reinterpret_cast<uint4*>(cd + c0) = v;
-            } else {
-                for (uint32_t t = c0; t < cend; ++t) cd[t] = t == idx ? 1 : 0;
-            }
-            continue;
-        }
-        // the vector sits in front of the payload: bytes [pay - k, pay) of the slot
-        const uint32_t v0 = pay - a.k;
-        if (wide && can_copy16(v0 + c0, pay + plen)) {
-            *reinterpret_cast<uint4*>(cd + c0) = load16(fslot, v0 + c0);
-        } else {
-            for (uint32_t t = c0; t < cend; ++t) cd[t] = fslot[v0 + t];
-        }
+        // the payload behind the vector is this kernel's to read as well
+        const bool wide = wide_block(cd, c0, a.k);
+        if (idx < a.k) unit_block(cd, c0, a.k, idx, wide);   // (vector_block, written out: see there)
+        else vector_copy_block(cd, c0, a.k, fslot, pay, pay + plen, wide);
     }
 }
-
-struct ParseHeadersArgs {
-    const uint8_t* frames;
-    uint64_t frame_stride;
-    const uint32_t* frame_len;
-    const uint32_t* frame_off;  // NULL: 0
-    const uint64_t* ids;
-    const uint32_t* n_frames;
-    uint16_t* row_index;
-    uint32_t* n_rows;
-    uint8_t* row_coeffs;
-    uint32_t* row_len;
-    uint32_t* row_off;
-    int32_t* frame_status;
-    uint32_t k, L, max_rows;
-};
 
 // one 256-thread block per generation; the decisions of k_parse_frames_coded,
 // the payloads left where they are: an accepted row is (row_off, row_len) into
@@ -494,58 +335,26 @@ __global__ void __launch_bounds__(256) k_parse_frame_headers(ParseHeadersArgs a)
     uint32_t base = 0;
     for (uint32_t s0 = 0; s0 < nf; s0 += blockDim.x) {
         const uint32_t s = s0 + threadIdx.x;
-        int32_t st = QF_OK;
-        uint32_t idx = 0xFFFF, pay = 0, plen = 0;
+        FrameHead h{QF_OK, 0xFFFF, 0, 0};
         if (s < nf) {
             const uint64_t fi = (uint64_t)g * a.max_rows + s;
-            const uint32_t flen = a.frame_len[fi];
-            const uint32_t foff = a.frame_off ? a.frame_off[fi] : 0;
-            const uint8_t* fr = a.frames + fi * a.frame_stride + foff;
-            uint32_t off = 0;
-            if (flen == 0 || (uint64_t)foff + flen > a.frame_stride) {
-                st = QF_EINVAL;  // "Raw data is empty", or not inside its slot
-            } else if (fr[0] == 1) {
-                off = 1;
-                idx = (uint32_t)(a.ids[fi] % a.k);  // decoder.rs:684
-            } else if (flen < 3) {
-                st = QF_ETOOSMALL;  // coefficient length missing (encoder.rs:33-38)
-            } else {
-                const uint32_t cl = ((uint32_t)fr[1] << 8) | fr[2];
-                if (flen < 3 + cl) st = QF_ETOOSMALL;  // coefficients truncated
-                else if (cl != a.k) st = QF_ERANGE;
-                off = 3 + cl;
-                idx = a.k;
-            }
-            if (st == QF_OK) {
-                plen = flen - off;
-                pay = foff + off;
-                // a payload that cannot be read in place: longer than L, or not
-                // at a multiple of 16 in its slot
-                if (plen > a.L || (pay & 15)) st = QF_EINVAL;
-            }
-            a.frame_status[fi] = st;
+            h = frame_head(a.frames + fi * a.frame_stride, a.frame_len[fi], a.frame_off ? a.frame_off[fi] : 0,
+                           a.frame_stride, a.ids + fi, a.k, a.L, true);
+            a.frame_status[fi] = h.st;
         }
-        const bool ok = s < nf && st == QF_OK;
-        // block-wide exclusive prefix of ok (4 waves)
-        const uint64_t bal = __ballot(ok);
-        const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-        const uint32_t before = __popcll(bal & ((lane == 0) ? 0ull : (~0ull >> (64 - lane))));
-        if (lane == 0) wave_cnt[w] = __popcll(bal);
-        __syncthreads();
-        uint32_t woff = 0;
-        for (uint32_t q = 0; q < w; ++q) woff += wave_cnt[q];
-        uint32_t total = 0;
-        for (uint32_t q = 0; q < 4; ++q) total += wave_cnt[q];
+        const bool ok = s < nf && h.st == QF_OK;
+        uint32_t total;
+        const uint32_t slot = base + block_prefix4(ok, wave_cnt, total);
         if (s < nf) {   // nf <= max_rows <= 1024
-            slot_of[s] = ok ? base + woff + before : 0xFFFFFFFFu;
-            pay_of[s] = pay;
-            idx_of[s] = (uint16_t)idx;
+            slot_of[s] = ok ? slot : 0xFFFFFFFFu;
+            pay_of[s] = h.pay;
+            idx_of[s] = (uint16_t)h.idx;
         }
         if (ok) {
-            const uint64_t o = (uint64_t)g * a.max_rows + base + woff + before;
-            a.row_index[o] = (uint16_t)idx;
-            a.row_len[o] = plen;
-            a.row_off[o] = (uint32_t)(s * a.frame_stride) + pay;   // max_rows * frame_stride <= 2^32
+            const uint64_t o = (uint64_t)g * a.max_rows + slot;
+            a.row_index[o] = (uint16_t)h.idx;
+            a.row_len[o] = h.plen;
+            a.row_off[o] = (uint32_t)(s * a.frame_stride) + h.pay;   // max_rows * frame_stride <= 2^32
         }
         base += total;
         __syncthreads();
@@ -563,94 +372,27 @@ __global__ void __launch_bounds__(256) k_parse_frame_headers(ParseHeadersArgs a)
         const uint64_t fi = (uint64_t)g * a.max_rows + s;
         const uint8_t* fslot = a.frames + fi * a.frame_stride;
         const uint32_t pay = pay_of[s];
-        const uint32_t c0 = u * 16;
-        const uint32_t cend = min(c0 + 16, a.k);
-        uint8_t* cd = a.row_coeffs + ((uint64_t)g * a.max_rows + slot) * a.k;
-        const uint32_t idx = idx_of[s];
-        const bool wide = c0 + 16 <= a.k && ((uintptr_t)(cd + c0) & 15) == 0;
-        if (idx < a.k) {
-            if (wide) {
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (idx >= c0 && idx < c0 + 16) {
-                    const uint32_t bit = 1u << (8 * (idx & 3));
-                    const uint32_t q = (idx - c0) >> 2;
-                    v.x = q == 0 ? bit : 0;
-                    v.y = q == 1 ? bit : 0;
-                    v.z = q == 2 ? bit : 0;
-                    v.w = q == 3 ? bit : 0;
-                }
-                *reinterpret_cast<uint4*>(cd + c0) = v;
-            } else {
-                for (uint32_t t = c0; t < cend; ++t) cd[t] = t == idx ? 1 : 0;
-            }
-            continue;
-        }
-        // the vector sits in front of the payload: bytes [pay - k, pay) of the
-        // slot; the readable bytes end with it (no payload byte is touched)
-        const uint32_t v0 = pay - a.k;
-        if (wide && can_copy16(v0 + c0, pay)) {
-            *reinterpret_cast<uint4*>(cd + c0) = load16(fslot, v0 + c0);
-        } else {
-            for (uint32_t t = c0; t < cend; ++t) cd[t] = fslot[v0 + t];
-        }
+        // the readable bytes end with the vector (no payload byte is touched)
+        vector_block(a.row_coeffs + ((uint64_t)g * a.max_rows + slot) * a.k, u * 16, a.k, idx_of[s], fslot, pay, pay);
     }
 }
 
 }  // namespace
 
-namespace qf {
-
-hipError_t launch_parse_frame_headers(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
-                                      const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
-                                      uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint16_t* row_index,
-                                      uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len, uint32_t* row_off,
-                                      int32_t* frame_status, hipStream_t st) {
-    ParseHeadersArgs a{};
-    a.frames = frames;
-    a.frame_stride = frame_stride;
-    a.frame_len = frame_len;
-    a.frame_off = frame_off;
-    a.ids = ids;
-    a.n_frames = n_frames;
-    a.row_index = row_index;
-    a.n_rows = n_rows;
-    a.row_coeffs = row_coeffs;
-    a.row_len = row_len;
-    a.row_off = row_off;
-    a.frame_status = frame_status;
-    a.k = k;
-    a.L = L;
-    a.max_rows = max_rows;
+hipError_t launch_parse_frame_headers(const ParseHeadersArgs& a, uint32_t G, hipStream_t st) {
     if (G == 0) return hipSuccess;
     hipLaunchKernelGGL(k_parse_frame_headers, dim3(G), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_frame_rows(const uint8_t* rows, const uint16_t* row_index, const uint32_t* n_rows,
-                             const uint8_t* row_coeffs, const uint32_t* row_len, const qf_frame_rows_shape& sh,
-                             uint32_t G, uint8_t* frames, uint32_t* frame_len, uint32_t* frame_off,
-                             const uint8_t* explog, int num_cus, hipStream_t st) {
-    FrameRowsArgs a{};
-    a.rows = rows;
-    a.row_index = row_index;
-    a.n_rows = n_rows;
-    a.row_coeffs = row_coeffs;
-    a.row_len = row_len;
-    a.frames = frames;
-    a.frame_len = frame_len;
-    a.frame_off = frame_off;
-    a.explog = explog;
-    a.row_stride = sh.row_stride;
-    a.rows_gen_stride = sh.rows_gen_stride;
-    a.frame_stride = sh.frame_stride;
-    a.k = sh.k;
-    a.r = sh.r;
-    a.L = sh.L;
-    a.max_rows = sh.max_rows;
-    a.P = qf_frame_payload_offset(sh.k);
+hipError_t launch_frame_rows(const FrameRowsArgs& args, uint32_t G, int num_cus, hipStream_t st) {
+    FrameRowsArgs a = args;
+    a.P = qf_frame_payload_offset(a.k);
     a.hdr_blocks = a.P / 16;
-    a.blocks_per_frame = a.hdr_blocks + ((sh.flags & QF_FRAME_IN_PLACE) ? 0 : (sh.L + 15) / 16);
-    a.total_blocks = (uint64_t)G * sh.max_rows * a.blocks_per_frame;
+    // rows == NULL selects in-place mode: qf_frame_rows_dev passes NULL for QF_FRAME_IN_PLACE and
+    // refuses a NULL rows in copy mode
+    a.blocks_per_frame = a.hdr_blocks + (a.rows ? (a.L + 15) / 16 : 0);
+    a.total_blocks = (uint64_t)G * a.max_rows * a.blocks_per_frame;
     if (a.total_blocks == 0) return hipSuccess;
     uint64_t blocks = (a.total_blocks + 255) / 256;
     const uint64_t cap = (uint64_t)num_cus * 8;
@@ -659,54 +401,16 @@ hipError_t launch_frame_rows(const uint8_t* rows, const uint16_t* row_index, con
     return hipGetLastError();
 }
 
-hipError_t launch_parse_frames_coded(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
-                                     const uint32_t* frame_off, const uint64_t* ids, const uint32_t* n_frames,
-                                     uint32_t k, uint32_t L, uint32_t G, uint32_t max_rows, uint8_t* rows,
-                                     uint64_t row_stride, uint64_t rows_gen_stride, uint16_t* row_index,
-                                     uint32_t* n_rows, uint8_t* row_coeffs, uint32_t* row_len,
-                                     int32_t* frame_status, hipStream_t st) {
-    ParseCodedArgs a{};
-    a.frames = frames;
-    a.frame_stride = frame_stride;
-    a.frame_len = frame_len;
-    a.frame_off = frame_off;
-    a.ids = ids;
-    a.n_frames = n_frames;
-    a.rows = rows;
-    a.row_stride = row_stride;
-    a.rows_gen_stride = rows_gen_stride;
-    a.row_index = row_index;
-    a.n_rows = n_rows;
-    a.row_coeffs = row_coeffs;
-    a.row_len = row_len;
-    a.frame_status = frame_status;
-    a.k = k;
-    a.L = L;
-    a.max_rows = max_rows;
+hipError_t launch_parse_frames_coded(const ParseCodedArgs& a, uint32_t G, hipStream_t st) {
     if (G == 0) return hipSuccess;
     hipLaunchKernelGGL(k_parse_frames_coded, dim3(G), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 
-hipError_t launch_frame_batch(const uint8_t* src, const uint8_t* rep, const qf_encode_shape& sh, uint32_t G,
-                              uint8_t* frames, uint64_t frame_stride, uint32_t* frame_len,
-                              const uint8_t* explog, int num_cus, hipStream_t st) {
-    FrameArgs a{};
-    a.src = src;
-    a.rep = rep;
-    a.src_row_stride = sh.src_row_stride;
-    a.src_gen_stride = sh.src_gen_stride;
-    a.rep_row_stride = sh.rep_row_stride;
-    a.rep_gen_stride = sh.rep_gen_stride;
-    a.frames = frames;
-    a.frame_stride = frame_stride;
-    a.frame_len = frame_len;
-    a.explog = explog;
-    a.k = sh.k;
-    a.r = sh.r;
-    a.L = sh.L;
-    a.blocks_per_frame = (uint32_t)((3 + sh.k + sh.L + 15) / 16);
-    a.total_blocks = (uint64_t)G * (sh.k + sh.r) * a.blocks_per_frame;
+hipError_t launch_frame_batch(const FrameArgs& args, uint32_t G, int num_cus, hipStream_t st) {
+    FrameArgs a = args;
+    a.blocks_per_frame = (uint32_t)((3 + a.k + a.L + 15) / 16);
+    a.total_blocks = (uint64_t)G * (a.k + a.r) * a.blocks_per_frame;
     if (a.total_blocks == 0) return hipSuccess;
     uint64_t blocks = (a.total_blocks + 255) / 256;
     const uint64_t cap = (uint64_t)num_cus * 8;
@@ -715,28 +419,7 @@ hipError_t launch_frame_batch(const uint8_t* src, const uint8_t* rep, const qf_e
     return hipGetLastError();
 }
 
-hipError_t launch_parse_frames(const uint8_t* frames, uint64_t frame_stride, const uint32_t* frame_len,
-                               const uint64_t* ids, const uint32_t* n_frames, uint32_t k, uint32_t r, uint32_t L,
-                               uint32_t G, uint32_t max_rows, uint8_t* rows, uint64_t row_stride,
-                               uint64_t rows_gen_stride, uint16_t* row_index, uint32_t* n_rows,
-                               int32_t* frame_status, const uint8_t* explog, hipStream_t st) {
-    ParseArgs a{};
-    a.frames = frames;
-    a.frame_stride = frame_stride;
-    a.frame_len = frame_len;
-    a.ids = ids;
-    a.n_frames = n_frames;
-    a.rows = rows;
-    a.row_stride = row_stride;
-    a.rows_gen_stride = rows_gen_stride;
-    a.row_index = row_index;
-    a.n_rows = n_rows;
-    a.frame_status = frame_status;
-    a.explog = explog;
-    a.k = k;
-    a.r = r;
-    a.L = L;
-    a.max_rows = max_rows;
+hipError_t launch_parse_frames(const ParseArgs& a, uint32_t G, hipStream_t st) {
     if (G == 0) return hipSuccess;
     hipLaunchKernelGGL(k_parse_frames, dim3(G), dim3(256), 0, st, a);
     return hipGetLastError();

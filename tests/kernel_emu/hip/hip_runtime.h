@@ -77,6 +77,11 @@ inline uint32_t atomicMin(uint32_t* p, uint32_t v) {
     return o;
 }
 #define __popcll __builtin_popcountll
+// v_alignbit_b32: the low dword of {hi, lo} >> (sh & 31)
+inline uint32_t emu_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) {
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (sh & 31));
+}
+#define __builtin_amdgcn_alignbit emu_alignbit
 
 template <class K, class A>
 void hipLaunchKernelGGL(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t, A args) {
