@@ -1088,6 +1088,117 @@ int qf_decode_partial_frames_sel_dev(qf_ctx *ctx, const qf_decode_frames_shape *
                                      uint16_t *src_slot_dev);
 
 /* ---------------------------------------------------------------------------
+ * Delivery: the source packets of a generation in source order, each once.  No
+ * reference counterpart.  A decode leaves a generation as a src_slot map into
+ * the row store, a rec_index list and rec rows; these two calls take those
+ * outputs and the store and write each generation's packets, in source order,
+ * into one contiguous output.  A small persistent "delivered" state per
+ * generation slot makes every source packet of a wire generation leave exactly
+ * once across deadline flushes, displacement and completion.
+ * Dense form: everything is indexed by g in 0..G-1.  Listed form: src_dev,
+ * row_off_dev, row_len_dev and delivered_dev are the arrays of sel->G_src
+ * generations, indexed by sel_dev[j]; every other argument is compact, indexed
+ * by the list position j and sized for n_max, exactly as
+ * qf_decode_frames_sel_dev and qf_decode_partial_frames_sel_dev leave their
+ * outputs and as qf_gen_window_sel_dev and evict_id_dev leave the ids.
+ * Per generation (entry) j, when dec_status_dev[j] is QF_OK or QF_ENOTREADY
+ * (both carry valid src_slot, n_rec and rec_index, from either decode):
+ *   S     = { i : src_slot_dev[j*k + i] != 0xFFFF }
+ *   D     = rec_index_dev[j*e_max + 0 .. n_rec_dev[j])
+ *   known = S u D;  new = known minus the sources marked in the delivered state.
+ * Delivered state (delivered_dev, nullable, 8-byte aligned, QF_DELIVERED_WORDS
+ * u64 per generation, zeroed once by the caller): word 0 is a tag, id + 1 of
+ * the wire generation the mask belongs to (0: empty); bit i of the 256 bits
+ * behind it is source i.  With ids_dev a tag other than ids_dev[j] + 1 means
+ * that the slot now holds another generation and the mask is taken as empty;
+ * when something is delivered the tag is rewritten with the new mask, so a
+ * slot that was displaced or reset needs no reset of this state.  An id of
+ * UINT64_MAX or >= 2^62 makes the entry QF_EINVAL.  With ids_dev NULL the tag
+ * is neither read nor written, and the caller zeroes a generation's words when
+ * it resets it.  With delivered_dev NULL every known source is new and ids_dev
+ * is ignored.  The state is written only when new is not empty.  With
+ * delivered_dev the listed entries must be distinct (for a duplicate the
+ * result is unspecified, every access stays in bounds: the rule of
+ * qf_rank_update_sel_batch); without it duplicates are legal.
+ * Outputs:
+ *   out_dev             for i in new the packet at j*out_gen_stride +
+ *                       i*out_row_stride: round_up(len, 16) bytes are written,
+ *                       those after len zero; len is the slot's row_len for a
+ *                       stored source and L for a recovered one.  No byte of
+ *                       any other row is written.
+ *   out_len_dev[j*k+i]  len for i in new, else 0
+ *   out_state_dev[j*k+i]  QF_SRC_STORED / QF_SRC_RECOVERED for i in new, else
+ *                       QF_SRC_EARLIER (marked in the state) or QF_SRC_UNKNOWN
+ *   n_out_dev[j]        |new|
+ *   n_known_dev[j]      (nullable) |known u the marked sources below k|
+ *   status_dev[j]       QF_OK: everything known has left.  QF_ENOTREADY:
+ *                       dec_status_dev[j] is another value or the entry is
+ *                       unused; all outputs zero, nothing read.  QF_EINVAL: an
+ *                       invalid entry (sel_dev[j] >= G_src), a bad id, or
+ *                       inconsistent inputs -- a src_slot value >= max_rows
+ *                       other than 0xFFFF, n_rec > e_max, a rec_index >= k, a
+ *                       source twice in rec_index or in both rec_index and S,
+ *                       a stored row (any source of S) with row_len > L,
+ *                       row_off % 16 != 0 or row_off + row_len >
+ *                       src_gen_stride; all outputs zero, no payload byte and
+ *                       no state touched.  Every index is checked before it is
+ *                       used.
+ * Reads: only aligned 16-byte units of a delivered row that hold one of its
+ * bytes, and no payload byte of a source that is not in new (so rec_dev must
+ * reach to the end of its last row's last unit: rec_row_stride bytes per row
+ * do).  src_dev and rec_dev are only read and must not overlap out_dev.
+ * Returns QF_EINVAL for k outside 1..256, e_max > 128, L == 0, max_rows
+ * outside 1..1024, flags or reserved != 0, G (n_max) > 2^24, a stride or
+ * src_dev / rec_dev / out_dev not 16-byte aligned, rec_row_stride < L,
+ * out_row_stride < round_up(L, 16), out_gen_stride < k * out_row_stride,
+ * delivered_dev not 8-byte aligned, a NULL required pointer (all but ids_dev,
+ * delivered_dev and n_known_dev; rec_dev and rec_index_dev only when e_max >
+ * 0), and in the listed form a NULL sel or sel_dev, n_max == 0 or G_src == 0.
+ * G == 0 is QF_OK.
+ * Kernels: k_deliver_prepare (one wave per entry: checks, sets, state, one
+ * record per delivered packet) and k_deliver_rows (the copy); no output
+ * depends on the order of waves.
+ * ------------------------------------------------------------------------- */
+#define QF_DELIVERED_WORDS 5   /* u64 per generation slot: tag, then 256 bits, bit i = source i */
+
+/* out_state values */
+#define QF_SRC_UNKNOWN   0  /* not determined by what the generation holds            */
+#define QF_SRC_STORED    1  /* delivered by this call from its systematic row         */
+#define QF_SRC_RECOVERED 2  /* delivered by this call from rec_dev                    */
+#define QF_SRC_EARLIER   3  /* determined, but delivered by an earlier call (not written) */
+
+typedef struct qf_deliver_shape {
+    uint32_t k;              /* 1..256 */
+    uint32_t e_max;          /* rec rows per generation: the decode's min(k, r), 0..128 */
+    uint32_t L;              /* >= 1, the decode's L */
+    uint32_t max_rows;       /* slots per generation of the source arrays (the store's cap), 1..1024 */
+    uint32_t flags;          /* 0 */
+    uint32_t reserved;       /* 0 */
+    uint64_t src_gen_stride; /* as the decode's */
+    uint64_t rec_row_stride; /* as the decode's */
+    uint64_t rec_gen_stride;
+    uint64_t out_row_stride; /* % 16 == 0, >= round_up(L, 16) */
+    uint64_t out_gen_stride; /* % 16 == 0, >= k * out_row_stride */
+} qf_deliver_shape;
+
+int qf_deliver_frames_dev(qf_ctx *ctx, const qf_deliver_shape *shape, uint32_t G,
+                          const uint8_t *src_dev, const uint32_t *row_off_dev,
+                          const uint32_t *row_len_dev, const uint8_t *rec_dev,
+                          const uint16_t *rec_index_dev, const uint32_t *n_rec_dev,
+                          const int32_t *dec_status_dev, const uint16_t *src_slot_dev,
+                          const uint64_t *ids_dev, uint64_t *delivered_dev,
+                          uint8_t *out_dev, uint32_t *out_len_dev, uint8_t *out_state_dev,
+                          uint32_t *n_out_dev, uint32_t *n_known_dev, int32_t *status_dev);
+int qf_deliver_frames_sel_dev(qf_ctx *ctx, const qf_deliver_shape *shape, const qf_gen_sel *sel,
+                              const uint8_t *src_dev, const uint32_t *row_off_dev,
+                              const uint32_t *row_len_dev, const uint8_t *rec_dev,
+                              const uint16_t *rec_index_dev, const uint32_t *n_rec_dev,
+                              const int32_t *dec_status_dev, const uint16_t *src_slot_dev,
+                              const uint64_t *ids_dev, uint64_t *delivered_dev,
+                              uint8_t *out_dev, uint32_t *out_len_dev, uint8_t *out_state_dev,
+                              uint32_t *n_out_dev, uint32_t *n_known_dev, int32_t *status_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations

@@ -101,6 +101,17 @@ class GenSel(ctypes.Structure):
     _fields_ = [("sel_dev", _P), ("n_sel_dev", _P), ("n_max", _U32), ("G_src", _U32)]
 
 
+class DeliverShape(ctypes.Structure):
+    """qf_deliver_shape (a decode's outputs and the store to packets in source order)."""
+    _fields_ = [
+        ("k", _U32), ("e_max", _U32), ("L", _U32), ("max_rows", _U32), ("flags", _U32), ("reserved", _U32),
+        ("src_gen_stride", _U64), ("rec_row_stride", _U64), ("rec_gen_stride", _U64),
+        ("out_row_stride", _U64), ("out_gen_stride", _U64),
+    ]
+
+
+QF_DELIVERED_WORDS = 5   # u64 per generation slot of the delivered state: tag, then 256 bits
+QF_SRC_UNKNOWN, QF_SRC_STORED, QF_SRC_RECOVERED, QF_SRC_EARLIER = 0, 1, 2, 3   # out_state of qf_deliver_frames_dev
 QF_SELECT_MARK = 1   # qf_gen_select_dev flags: seen[g] = rank[g] for the selected generations
 QF_WINDOW_CLOSE = 1  # qf_gen_window_sel_dev flags: set the closed flag of the listed entries
 QF_GEN_NONE = 0xFFFFFFFF   # qf_gen_window_dev: the tag of a frame that is dropped
@@ -261,6 +272,8 @@ _SIGS = {
                                      _P, _P, _P, _P, _P, _P, _P, _P]),
     "qf_gen_window_dev": (_I, [_P, _U32, _U32, _P, _P, _P, _U32, _P, _P, _U32, _P, _P, _P]),
     "qf_gen_window_sel_dev": (_I, [_P, ctypes.POINTER(GenSel), _P, _U32, _P]),
+    "qf_deliver_frames_dev": (_I, [_P, ctypes.POINTER(DeliverShape), _U32] + [_P] * 16),
+    "qf_deliver_frames_sel_dev": (_I, [_P, ctypes.POINTER(DeliverShape), ctypes.POINTER(GenSel)] + [_P] * 16),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

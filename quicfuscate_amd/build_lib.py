@@ -31,7 +31,7 @@ LIB_ROCM = OUT_DIR / "libqf_fec_rocm.so"
 SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_adaptive.hip", "qf_wire.hip",
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
            "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip", "qf_select.hip",
-           "qf_poll.hip", "qf_window.hip", "qf_partial.hip"]
+           "qf_poll.hip", "qf_window.hip", "qf_partial.hip", "qf_deliver.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -188,6 +188,11 @@ RESOURCE_RULES = {
     # the partial decode's control kernel keeps its matrix in LDS and a few
     # counters per lane: no scratch
     "qf_partial.hip": _Rule(("k_partial_prepare",), 1, every=True),
+    # the delivery's control kernel holds four sources per lane and its counts
+    # in LDS, the copy four addresses and four 16-byte units per lane
+    # (DESIGN.md 3.19): no scratch, in the control kernel's two forms (dense and
+    # over a list) and in the copy
+    "qf_deliver.hip": _Rule(("k_deliver_prepare", "k_deliver_rows"), 3, every=True),
 }
 # the sources compiled with resource-usage remarks
 REMARK_SOURCES = ("qf_gf16_bs.hip", *RESOURCE_RULES)

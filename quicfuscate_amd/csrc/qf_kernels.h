@@ -164,6 +164,56 @@ size_t prepare_lds_bytes(uint32_t k, uint32_t e_max, uint32_t max_rows);
 // generation with no determined source, or of another status, records none.
 hipError_t launch_partial_prepare(const PrepareArgs& a, hipStream_t st);
 size_t partial_prepare_lds_bytes(uint32_t k, uint32_t max_rows);
+// qf_deliver_frames_dev / qf_deliver_frames_sel_dev (qf_deliver.hip; DESIGN.md
+// 3.19).  The blocks of k_deliver_prepare are the G entries; with sel the
+// source side (row_off, row_len, delivered, and the record's offset into src)
+// is indexed by the listed generation sel[j] < G_src and everything else by
+// the list position.  One 16-byte record per delivered packet, compacted in
+// ascending source order at rec + j * k:
+//   {offset low, offset high | kDeliverFromRec, length, source index}
+// the offset from src (from rec_rows with kDeliverFromRec), and cnt[j] records
+// (0 for an entry that delivers nothing).
+constexpr uint32_t kDeliverFromRec = 0x80000000u;
+constexpr uint32_t kDeliverPrepareLds = 256 * 4 + 256 * 2;
+constexpr uint32_t kDeliverGroupsPerCu = 16;   // the copy's grid bound: workgroups per CU
+struct DeliverPrepareArgs {
+    const uint32_t* row_off;      // [G_src][max_rows]
+    const uint32_t* row_len;
+    const uint16_t* rec_index;    // [G][e_max]
+    const uint32_t* n_rec;        // [G]
+    const int32_t* dec_status;    // [G]
+    const uint16_t* src_slot;     // [G][k]
+    const uint64_t* ids;          // [G] or nullptr
+    uint64_t* delivered;          // [G_src][5] or nullptr
+    uint32_t* out_len;            // [G][k]
+    uint8_t* out_state;           // [G][k]
+    uint32_t* n_out;              // [G]
+    uint32_t* n_known;            // [G] or nullptr
+    int32_t* status;              // [G]
+    uint4* rec;                   // [G][k]
+    uint32_t* cnt;                // [G]
+    uint64_t src_gen_stride, rec_row_stride, rec_gen_stride;
+    uint32_t k, e_max, L, max_rows, G;
+    const uint32_t* sel = nullptr;
+    const uint32_t* n_sel = nullptr;   // nullptr: G
+    uint32_t G_src = 0;
+};
+// The copy: wave w of the launch takes the quads q = w, w + n_waves, ... below
+// n_quads = G * kq, quad q being records 4 (q % kq) .. + 3 of entry q / kq
+// (kq = ceil(k / 4)).  round_up(length, 16) bytes per record, the bytes at and
+// after the length zero, to out + j * out_gen_stride + source * out_row_stride.
+struct DeliverRowsArgs {
+    const uint8_t* src;
+    const uint8_t* rec_rows;
+    uint8_t* out;
+    const uint4* rec;
+    const uint32_t* cnt;
+    uint64_t out_row_stride, out_gen_stride;
+    uint32_t k, kq, n_quads, n_waves;
+};
+hipError_t launch_deliver_prepare(const DeliverPrepareArgs& a, hipStream_t st);
+// grid_cap: the most workgroups (of four waves) to launch; the rest is strided
+hipError_t launch_deliver_rows(DeliverRowsArgs a, uint32_t G, uint32_t grid_cap, hipStream_t st);
 hipError_t launch_mul_slice(const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n,
                             const uint8_t* explog, int num_cus, hipStream_t st);
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t n, uint64_t seed, uint64_t word_offset,

@@ -929,6 +929,82 @@ def gen_window_sel(sel, n_sel, win, *, n_max: int, G_src: int, ids=None, close: 
         ctx.handle, ctypes.byref(gs), _ptr(win), QF_WINDOW_CLOSE if close else 0, _opt(ids)), "gen_window_sel")
 
 
+QF_DELIVERED_WORDS = L.QF_DELIVERED_WORDS
+QF_SRC_UNKNOWN, QF_SRC_STORED, QF_SRC_RECOVERED, QF_SRC_EARLIER = (L.QF_SRC_UNKNOWN, L.QF_SRC_STORED,
+                                                                   L.QF_SRC_RECOVERED, L.QF_SRC_EARLIER)
+
+
+def _need_deliver(G: int, k: int, em: int, Lb: int, rec, rec_index, n_rec, dec_status, src_slot, ids, out, out_len,
+                  out_state, n_out, n_known, status, rec_row_stride: int, rec_gen_stride: int, out_row_stride: int,
+                  out_gen_stride: int) -> None:
+    """_need for the arguments of deliver_frames that are indexed by the
+    generation (dense) or by the list position (listed)."""
+    _need(rec, _span(G, rec_gen_stride, em, rec_row_stride, (Lb + 15) // 16 * 16), "rec (read in whole 16-byte units)")
+    _need(rec_index, 2 * G * em, "rec_index (e_max entries per generation)")
+    _need(n_rec, 4 * G, "n_rec")
+    _need(dec_status, 4 * G, "dec_status")
+    _need(src_slot, 2 * G * k, "src_slot")
+    _need(ids, 8 * G, "ids")
+    _need(out, _span(G, out_gen_stride, k, out_row_stride, (Lb + 15) // 16 * 16), "out")
+    _need(out_len, 4 * G * k, "out_len")
+    _need(out_state, G * k, "out_state")
+    _need(n_out, 4 * G, "n_out")
+    _need(n_known, 4 * G, "n_known")
+    _need(status, 4 * G, "status")
+
+
+def deliver_frames(src, row_off, row_len, rec, rec_index, n_rec, dec_status, src_slot, out, out_len, out_state, n_out,
+                   status, k: int, e_max: int, Lb: int, *, max_rows: int, src_gen_stride: int, rec_row_stride: int,
+                   rec_gen_stride: int, out_row_stride: int, out_gen_stride: int, G: int, ids=None, delivered=None,
+                   n_known=None, ctx: Optional[Context] = None) -> None:
+    """qf_deliver_frames_dev: the outputs of decode_frames / decode_partial_frames
+    (rec, rec_index, n_rec, their status as dec_status, src_slot; e_max their
+    min(k, r)) and the rows they read (src, row_off, row_len) to packets in
+    source order: source i of generation g at out + g*out_gen_stride +
+    i*out_row_stride, out_len [G, k] u32 its length and out_state [G, k] u8 one
+    of QF_SRC_*.  delivered: optional [G, QF_DELIVERED_WORDS] u64 state, zeroed
+    once, with which a source of a wire generation (ids [G] u64) leaves once
+    across calls; n_out [G] the packets this call wrote, n_known [G] (optional)
+    those known so far."""
+    _need(src, G * src_gen_stride, "src")
+    _need_rows(G, max_rows, k, row_off, row_len, None, None, None)
+    _need(delivered, 8 * QF_DELIVERED_WORDS * G, "delivered (QF_DELIVERED_WORDS u64 per generation)")
+    _need_deliver(G, k, e_max, Lb, rec, rec_index, n_rec, dec_status, src_slot, ids, out, out_len, out_state, n_out,
+                  n_known, status, rec_row_stride, rec_gen_stride, out_row_stride, out_gen_stride)
+    ctx = ctx or default_context()
+    sh = L.DeliverShape(k, e_max, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride, out_row_stride,
+                        out_gen_stride)
+    check(L._lib().qf_deliver_frames_dev(
+        ctx.handle, ctypes.byref(sh), G, _opt(src), _opt(row_off), _opt(row_len), _opt(rec), _opt(rec_index),
+        _opt(n_rec), _opt(dec_status), _opt(src_slot), _opt(ids), _opt(delivered), _opt(out), _opt(out_len),
+        _opt(out_state), _opt(n_out), _opt(n_known), _opt(status)), "deliver_frames")
+
+
+def deliver_frames_sel(sel, n_sel, src, row_off, row_len, rec, rec_index, n_rec, dec_status, src_slot, out, out_len,
+                       out_state, n_out, status, k: int, e_max: int, Lb: int, *, n_max: int, G_src: int,
+                       max_rows: int, src_gen_stride: int, rec_row_stride: int, rec_gen_stride: int,
+                       out_row_stride: int, out_gen_stride: int, ids=None, delivered=None, n_known=None,
+                       ctx: Optional[Context] = None) -> None:
+    """qf_deliver_frames_sel_dev: deliver_frames over a list.  src, row_off,
+    row_len and delivered hold G_src generations and are indexed by sel[j];
+    everything else is indexed by the list position, as decode_frames_sel and
+    decode_partial_frames_sel leave their outputs and gen_window_sel /
+    gen_window's evict_id the ids."""
+    _need(src, G_src * src_gen_stride, "src")
+    _need_rows(G_src, max_rows, k, row_off, row_len, None, None, None)
+    _need(delivered, 8 * QF_DELIVERED_WORDS * G_src, "delivered (QF_DELIVERED_WORDS u64 per generation)")
+    _need_deliver(n_max, k, e_max, Lb, rec, rec_index, n_rec, dec_status, src_slot, ids, out, out_len, out_state,
+                  n_out, n_known, status, rec_row_stride, rec_gen_stride, out_row_stride, out_gen_stride)
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    sh = L.DeliverShape(k, e_max, Lb, max_rows, 0, 0, src_gen_stride, rec_row_stride, rec_gen_stride, out_row_stride,
+                        out_gen_stride)
+    check(L._lib().qf_deliver_frames_sel_dev(
+        ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _opt(src), _opt(row_off), _opt(row_len), _opt(rec),
+        _opt(rec_index), _opt(n_rec), _opt(dec_status), _opt(src_slot), _opt(ids), _opt(delivered), _opt(out),
+        _opt(out_len), _opt(out_state), _opt(n_out), _opt(n_known), _opt(status)), "deliver_frames_sel")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
