@@ -1199,6 +1199,105 @@ int qf_deliver_frames_sel_dev(qf_ctx *ctx, const qf_deliver_shape *shape, const 
                               uint32_t *n_out_dev, uint32_t *n_known_dev, int32_t *status_dev);
 
 /* ---------------------------------------------------------------------------
+ * Streaming send: the listed rows as a flat frame queue.  No reference
+ * counterpart.  The mirror of qf_parse_poll_headers_dev: it takes compact rows
+ * by list position -- what qf_recode_frames_sel_dev leaves, or a source's
+ * packets -- and appends each entry's frames to a flat queue of N_max frame
+ * slots without a hole, with an emission budget per generation.  The queue's
+ * arrays (frames_dev, frame_len_dev, frame_off_dev, frame_id_dev,
+ * frame_pkt_dev, n_frames_dev) are exactly the flat poll that
+ * qf_gen_window_dev (ids = frame_id_dev) and qf_parse_poll_headers_dev
+ * (ids = frame_pkt_dev) of the next hop read, so a hop needs no host scan.
+ * Inputs, indexed by the list position j in 0..n_max-1 (the input layout of
+ * qf_frame_rows_dev with G = n_max): rows_dev (row s of entry j at
+ * j*rows_gen_stride + s*row_stride), row_index_dev (nullable: every row coded),
+ * n_rows_dev (nullable: max_rows), row_coeffs_dev ([n_max][max_rows][k];
+ * nullable when row_index_dev is given), row_len_dev (nullable: L),
+ * in_status_dev (nullable; the recode's status_dev) and ids_dev (the wire
+ * generation ids, as qf_gen_window_sel_dev writes them).  rank_dev and sent_dev
+ * (both or neither) are persistent arrays of sel->G_src generations, indexed by
+ * sel_dev[j]: the budget.
+ * Per entry j, with n = min(*n_sel_dev, n_max) and n_j = min(n_rows_dev[j],
+ * max_rows), the first that applies:
+ *   j >= n (unused)                       QF_ENOTREADY, count 0
+ *   sel_dev[j] >= G_src, ids_dev[j] >= 2^62 (UINT64_MAX included), one of the
+ *   first n_j rows with row_len > L or with index >= k while row_coeffs_dev is
+ *   NULL (invalid)                        QF_EINVAL, count 0; nothing is read
+ *                                         through a bad sel or id
+ *   in_status_dev[j] != QF_OK             that status, count 0
+ *   otherwise the entry wants c_j = n_j frames, with the budget c_j = min(n_j,
+ *   rank_dev[g] - sent_dev[g]) (0 when rank <= sent), g = sel_dev[j]: its first
+ *   c_j rows.
+ * The queue: base = min(*n_frames_dev, N_max) with QF_EMIT_APPEND, else 0
+ * (*n_frames_dev is then not read).  P_j = the sum of c over the entries before
+ * j.  Entry j is emitted iff base + P_j + c_j <= N_max; P_j only grows, so the
+ * emitted entries are a prefix of the wanting ones and the queue has no hole.
+ * Row s of an emitted entry is frame base + P_j + s.
+ *   entry_status_dev[j]  QF_OK for an emitted entry (also one with c_j = 0),
+ *                        QF_ENOTREADY for one that does not fit, else as above
+ *   entry_count_dev[j]   c_j for an emitted entry, else 0
+ *   entry_first_dev[j]   base + P_j, 0xFFFFFFFF whenever the count is 0
+ *   *n_frames_dev        the queue's new length: base + the emitted frames
+ *   *n_left_dev          (nullable) the wanted frames that did not fit
+ *                        (0xFFFFFFFF for more)
+ *   sent_dev[g]          += c_j for emitted entries only: an entry that did not
+ *                        fit leaves with a later call, qf_gen_select_dev(rank_dev,
+ *                        seen_dev = sent_dev, min_rank 1, flags 0) lists exactly
+ *                        the generations with budget left, and
+ *                        qf_stream_reset_dev(seen_dev = sent_dev) clears it
+ * With sent_dev the valid entries must be distinct (for a duplicate the result
+ * is unspecified, every access stays in bounds: the rule of
+ * qf_rank_update_sel_batch).
+ * Per frame f in [base, *n_frames_dev), row s of entry j: the slot's bytes,
+ * frame_len_dev[f] and frame_off_dev[f] are byte for byte what
+ * qf_frame_rows_dev writes in copy mode for that row (the payload at byte P =
+ * qf_frame_payload_offset(k) of slot f, the header in front of it; no byte of
+ * the slot outside the frame is written); frame_id_dev[f] = ids_dev[j];
+ * frame_pkt_dev[f] = the row's index for a systematic row and 0 for a coded
+ * one, so that id % k in the parsers is the source index.  Nothing is written
+ * below base or at and beyond the new length.
+ * Reads: the metadata of the first n_j rows of entries with a valid sel and id;
+ * of emitted rows only, the aligned 16-byte payload units that hold a byte of
+ * the row (rows_dev must reach to the end of its last row's last unit) and
+ * bytes of the row's own k-byte vector, through aligned dwords that lie inside
+ * it, or singly.  rows_dev is only read and must not overlap frames_dev.
+ * Returns QF_EINVAL for k outside 1..256, L == 0, max_rows outside 1..1024,
+ * N_max == 0, unknown flag bits, reserved != 0, a stride or rows_dev /
+ * frames_dev not 16-byte aligned, row_stride < L, frame_stride < P + L,
+ * N_max * frame_stride > 2^32, one of rank_dev / sent_dev without the other,
+ * row_index_dev and row_coeffs_dev both NULL, a NULL required pointer (all but
+ * the nullable ones above), a NULL sel or sel_dev, n_max == 0, n_max > 2^24 or
+ * G_src == 0.
+ * Kernels: k_emit_count and k_emit_place (checks, counts and their prefix in
+ * two launches as in qf_gen_select_dev, no workgroup waits for another) and
+ * k_emit_frames (the bytes: four frames per wave); no output depends on the
+ * order of waves or on atomics.
+ * ------------------------------------------------------------------------- */
+#define QF_EMIT_APPEND 1u   /* qf_emit_shape.flags: append at *n_frames_dev instead of starting at 0 */
+
+typedef struct qf_emit_shape {
+    uint32_t k;               /* 1..256 */
+    uint32_t L;               /* >= 1, the longest row */
+    uint32_t max_rows;        /* rows per entry, 1..1024 */
+    uint32_t N_max;           /* frame slots of the queue, >= 1 */
+    uint32_t flags;           /* 0 or QF_EMIT_APPEND */
+    uint32_t reserved;        /* 0 */
+    uint64_t row_stride;      /* % 16 == 0, >= L */
+    uint64_t rows_gen_stride; /* % 16 == 0 */
+    uint64_t frame_stride;    /* % 16 == 0, >= P + L, N_max * frame_stride <= 2^32 */
+} qf_emit_shape;
+
+int qf_emit_frames_sel_dev(qf_ctx *ctx, const qf_emit_shape *shape, const qf_gen_sel *sel,
+                           const uint8_t *rows_dev, const uint16_t *row_index_dev,
+                           const uint32_t *n_rows_dev, const uint8_t *row_coeffs_dev,
+                           const uint32_t *row_len_dev, const int32_t *in_status_dev,
+                           const uint64_t *ids_dev, const uint32_t *rank_dev, uint32_t *sent_dev,
+                           uint8_t *frames_dev, uint32_t *frame_len_dev, uint32_t *frame_off_dev,
+                           uint64_t *frame_id_dev, uint64_t *frame_pkt_dev, uint32_t *n_frames_dev,
+                           uint32_t *n_left_dev, uint32_t *entry_first_dev,
+                           uint32_t *entry_count_dev, int32_t *entry_status_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations
@@ -1560,6 +1659,15 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
  * recode, and qf_stream_reset_dev twice: once for state_dev, store_n_dev and
  * seen_dev, once more with seen_dev = rank_dev (the other two NULL), which
  * clears the listed generations' ranks.
+ * The send step of a relay, behind the append: qf_gen_select_dev(rank_dev,
+ * seen_dev = sent_dev, min_rank 1, flags 0) lists the generations with budget
+ * left, then
+ *   qf_recode_frames_sel_dev    m fresh combinations per listed generation, compact by list position
+ *   qf_gen_window_sel_dev       flags 0: the listed generations' wire ids
+ *   qf_emit_frames_sel_dev      the first min(m, rank - sent) rows of each as frames, one behind the
+ *                               other in a flat queue; sent_dev grows by what was emitted
+ * and the queue's arrays are the flat poll of the next hop.  A source emits its
+ * packets as systematic rows, then its repairs with QF_EMIT_APPEND.
  * The intermediate rows belong to the caller.
  * ------------------------------------------------------------------------- */
 /* No reference counterpart (a layout rule): P = round_up(3 + k, 16) for k in

@@ -110,6 +110,15 @@ class DeliverShape(ctypes.Structure):
     ]
 
 
+class EmitShape(ctypes.Structure):
+    """qf_emit_shape (the listed rows to a flat frame queue)."""
+    _fields_ = [
+        ("k", _U32), ("L", _U32), ("max_rows", _U32), ("N_max", _U32), ("flags", _U32), ("reserved", _U32),
+        ("row_stride", _U64), ("rows_gen_stride", _U64), ("frame_stride", _U64),
+    ]
+
+
+QF_EMIT_APPEND = 1   # qf_emit_shape.flags: append at *n_frames_dev instead of starting at 0
 QF_DELIVERED_WORDS = 5   # u64 per generation slot of the delivered state: tag, then 256 bits
 QF_SRC_UNKNOWN, QF_SRC_STORED, QF_SRC_RECOVERED, QF_SRC_EARLIER = 0, 1, 2, 3   # out_state of qf_deliver_frames_dev
 QF_SELECT_MARK = 1   # qf_gen_select_dev flags: seen[g] = rank[g] for the selected generations
@@ -274,6 +283,7 @@ _SIGS = {
     "qf_gen_window_sel_dev": (_I, [_P, ctypes.POINTER(GenSel), _P, _U32, _P]),
     "qf_deliver_frames_dev": (_I, [_P, ctypes.POINTER(DeliverShape), _U32] + [_P] * 16),
     "qf_deliver_frames_sel_dev": (_I, [_P, ctypes.POINTER(DeliverShape), ctypes.POINTER(GenSel)] + [_P] * 16),
+    "qf_emit_frames_sel_dev": (_I, [_P, ctypes.POINTER(EmitShape), ctypes.POINTER(GenSel)] + [_P] * 19),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

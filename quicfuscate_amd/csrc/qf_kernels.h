@@ -214,6 +214,55 @@ struct DeliverRowsArgs {
 hipError_t launch_deliver_prepare(const DeliverPrepareArgs& a, hipStream_t st);
 // grid_cap: the most workgroups (of four waves) to launch; the rest is strided
 hipError_t launch_deliver_rows(DeliverRowsArgs a, uint32_t G, uint32_t grid_cap, hipStream_t st);
+// qf_emit_frames_sel_dev (qf_emit.hip).  k_emit_count leaves
+// every entry's wanted frame count in want and its status so far in
+// entry_status, each block's sum in sums and the queue's base in head[0];
+// k_emit_place derives every entry's position from them, writes the per-entry
+// and per-frame outputs, the emitted frame count in head[1] and one 16-byte
+// record per emitted frame, in queue order from the base:
+//   {list position, row, row length, row index (k for a coded row)}
+constexpr uint32_t kEmitPerBlock = 64;                 // entries of a block (one wave, one entry per lane)
+constexpr uint32_t kEmitGroupsPerCu = 16;              // the copy's grid bound: workgroups per CU
+struct EmitPlanArgs {
+    const uint32_t* sel;          // [n_max]
+    const uint32_t* n_sel;        // nullptr: n_max
+    const uint16_t* row_index;    // [n_max][max_rows] or nullptr: every row coded
+    const uint32_t* n_rows;       // [n_max] or nullptr: max_rows
+    const uint32_t* row_len;      // [n_max][max_rows] or nullptr: L
+    const int32_t* in_status;     // [n_max] or nullptr
+    const uint64_t* ids;          // [n_max]
+    const uint32_t* rank;         // [G_src] or nullptr, with sent
+    uint32_t* sent;               // [G_src] or nullptr
+    uint32_t* frame_len;          // [N_max]
+    uint32_t* frame_off;
+    uint64_t* frame_id;
+    uint64_t* frame_pkt;
+    uint32_t* n_frames;
+    uint32_t* n_left;             // nullable
+    uint32_t* entry_first;        // [n_max]
+    uint32_t* entry_count;
+    int32_t* entry_status;
+    uint32_t* want;               // workspace [n_max]
+    uint32_t* sums;               // workspace [blocks]
+    uint32_t* head;               // workspace [2]: base, emitted
+    uint4* rec;                   // workspace [min(n_max * max_rows, N_max)]
+    uint32_t n_max, G_src, k, L, max_rows, N_max, P, append, has_coeffs, blocks;
+};
+// The copy: wave w takes the quads q = w, w + n_waves, ... of the head[1]
+// records, quad q being records 4q .. 4q + 3, frames head[0] + 4q .. of the queue.
+struct EmitFramesArgs {
+    const uint8_t* rows;
+    const uint8_t* row_coeffs;    // nullptr: no coded row among the records
+    uint8_t* frames;
+    const uint4* rec;
+    const uint32_t* head;
+    uint64_t row_stride, rows_gen_stride, frame_stride;
+    uint32_t k, P, max_rows, n_waves;
+};
+hipError_t launch_emit_count(const EmitPlanArgs& a, hipStream_t st);
+hipError_t launch_emit_place(const EmitPlanArgs& a, hipStream_t st);   // after launch_emit_count, same stream
+// max_frames: the most frames the plan can have emitted; grid_cap as above
+hipError_t launch_emit_frames(EmitFramesArgs a, uint64_t max_frames, uint32_t grid_cap, hipStream_t st);
 hipError_t launch_mul_slice(const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n,
                             const uint8_t* explog, int num_cus, hipStream_t st);
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t n, uint64_t seed, uint64_t word_offset,

@@ -1005,6 +1005,54 @@ def deliver_frames_sel(sel, n_sel, src, row_off, row_len, rec, rec_index, n_rec,
         _opt(out_len), _opt(out_state), _opt(n_out), _opt(n_known), _opt(status)), "deliver_frames_sel")
 
 
+QF_EMIT_APPEND = L.QF_EMIT_APPEND
+
+
+def emit_frames_sel(sel, n_sel, rows, ids, frames, frame_len, frame_off, frame_id, frame_pkt, n_frames, entry_first,
+                    entry_count, entry_status, k: int, Lb: int, *, n_max: int, G_src: int, max_rows: int, N_max: int,
+                    row_stride: int, rows_gen_stride: int, frame_stride: int, row_index=None, n_rows=None,
+                    row_coeffs=None, row_len=None, in_status=None, rank=None, sent=None, n_left=None,
+                    append: bool = False, ctx: Optional[Context] = None) -> None:
+    """qf_emit_frames_sel_dev: the compact rows of a list (rows, row_index,
+    n_rows, row_coeffs, row_len and in_status by list position, as
+    recode_frames_sel leaves them; ids [n_max] u64 as gen_window_sel writes
+    them) appended to a flat queue of N_max frame slots: frames, frame_len,
+    frame_off [N_max] u32, frame_id and frame_pkt [N_max] u64, n_frames [1],
+    which are the flat poll gen_window and parse_poll_headers read.  rank and
+    sent ([G_src] u32, both or neither) are the budget: an entry emits at most
+    rank[sel[j]] - sent[sel[j]] frames and sent grows by what it emitted.
+    entry_first, entry_count and entry_status [n_max] say where each entry's
+    frames went; n_left [1] (optional) counts the wanted frames that did not
+    fit.  append: start at n_frames[0] instead of 0."""
+    P = frame_payload_offset(k)
+    _need(rows, _span(n_max, rows_gen_stride, max_rows, row_stride, (Lb + 15) // 16 * 16),
+          "rows (read in whole 16-byte units)")
+    _need_rows(n_max, max_rows, k, None, row_len, row_index, row_coeffs, n_rows)
+    _need(in_status, 4 * n_max, "in_status")
+    _need(ids, 8 * n_max, "ids")
+    _need(rank, 4 * G_src, "rank")
+    _need(sent, 4 * G_src, "sent")
+    _need(frames, _span(N_max, frame_stride, 1, 0, P + Lb), "frames")
+    _need(frame_len, 4 * N_max, "frame_len")
+    _need(frame_off, 4 * N_max, "frame_off")
+    _need(frame_id, 8 * N_max, "frame_id")
+    _need(frame_pkt, 8 * N_max, "frame_pkt")
+    _need(n_frames, 4, "n_frames")
+    _need(n_left, 4, "n_left")
+    _need(entry_first, 4 * n_max, "entry_first")
+    _need(entry_count, 4 * n_max, "entry_count")
+    _need(entry_status, 4 * n_max, "entry_status")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    sh = L.EmitShape(k, Lb, max_rows, N_max, QF_EMIT_APPEND if append else 0, 0, row_stride, rows_gen_stride,
+                     frame_stride)
+    check(L._lib().qf_emit_frames_sel_dev(
+        ctx.handle, ctypes.byref(sh), ctypes.byref(gs), _opt(rows), _opt(row_index), _opt(n_rows), _opt(row_coeffs),
+        _opt(row_len), _opt(in_status), _opt(ids), _opt(rank), _opt(sent), _opt(frames), _opt(frame_len),
+        _opt(frame_off), _opt(frame_id), _opt(frame_pkt), _opt(n_frames), _opt(n_left), _opt(entry_first),
+        _opt(entry_count), _opt(entry_status)), "emit_frames_sel")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
