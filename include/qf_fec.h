@@ -1298,6 +1298,115 @@ int qf_emit_frames_sel_dev(qf_ctx *ctx, const qf_emit_shape *shape, const qf_gen
                            uint32_t *entry_count_dev, int32_t *entry_status_dev);
 
 /* ---------------------------------------------------------------------------
+ * Streaming feedback: rank reports and the credit budget.  No reference
+ * counterpart.  A receiver tells its sender what it holds of a generation in a
+ * 16-byte record; the sender turns its own ranks, a redundancy ratio and those
+ * records into credit_dev, the array that qf_gen_select_dev and
+ * qf_emit_frames_sel_dev take as rank_dev beside sent_dev: "the number of
+ * frames a generation may have sent in total".  How the records travel back is
+ * the host's business, as the outer header of a frame is.
+ *   id        a wire generation id (< 2^62); UINT64_MAX is a hole the applier
+ *             skips (with status QF_EINVAL)
+ *   rank      what the reporting node holds of it, 0..k; k for a generation it
+ *             has delivered and closed
+ *   reserved  0
+ *
+ * qf_rank_report_sel_dev: the ranks of a list as reports.  n = min(*n_sel_dev,
+ * n_max) (n_max with n_sel_dev NULL); base = min(*n_reports_dev, N_max) with
+ * QF_REPORT_APPEND, else 0 (*n_reports_dev is then not read).  The record of
+ * entry j < n goes to reports_dev[base + j] when base + j < N_max; for slot s =
+ * sel_dev[j] it is
+ *   s >= G_src, or win_dev[s] empty        {UINT64_MAX, 0, 0}
+ *   win_dev[s] open                         {its id, min(rank_dev[s], k), 0}
+ *   win_dev[s] closed                       {its id, k, 0}  (the closing reset
+ *                                           zeroed the rank: the window
+ *                                           remembers it)
+ * *n_reports_dev = min(base + n, N_max); *n_left_dev (nullable) = the records
+ * that did not fit, base + n - *n_reports_dev.  Nothing is written below base or
+ * at and beyond the new length; win_dev and rank_dev are only read; a sel value
+ * at or behind n is not looked at and nothing is read through one >= G_src.
+ * Duplicates in the list give duplicate records.  Meant for the completed list
+ * after qf_gen_window_sel_dev(QF_WINDOW_CLOSE) has closed it and, appended, for
+ * the list of qf_gen_select_dev(rank_dev, NULL, min_rank 1, flags 0) after the
+ * resets: every open generation that holds a row.
+ * Returns QF_EINVAL for k outside 1..256, a NULL ctx, sel, sel_dev, win_dev,
+ * rank_dev, reports_dev or n_reports_dev, n_max == 0, G_src == 0, N_max == 0,
+ * unknown flag bits, or reports_dev not 16-byte aligned.
+ * One kernel, k_report_sel, a lane per entry (an appending call copies
+ * *n_reports_dev in front of it).
+ *
+ * qf_credit_update_dev: credit_dev[s] for every slot s < G, every call.
+ * fb_state_dev holds 16 bytes per slot, {u64 owner; u32 peer; u32 reserved},
+ * zeroed once by the caller and then owned by this call: owner is the id + 1 of
+ * the generation the state belongs to (0: none), peer the highest rank reported
+ * for it.  credit_dev is read as the previous credit of a slot whose state
+ * belongs to the generation the slot holds, and is not read otherwise (so it
+ * needs no initialisation).
+ * Reports: N = min(*n_reports_dev, N_max) (N_max with n_reports_dev NULL).  For
+ * f < N, with s = id % G, the first that applies:
+ *   id >= 2^62, rank > k or reserved != 0         QF_EINVAL (nothing is read
+ *                                                 through the id)
+ *   win_dev[s] holds a larger id                  QF_ESTALE
+ *   win_dev[s] is empty or holds a smaller id     QF_ENOTREADY
+ *   win_dev[s] holds this id, open or closed      QF_OK
+ * in report_status_dev[f] (nullable).  Reports at and above N are not looked at
+ * and their status is not written.
+ * Per slot s: an empty win_dev[s] gives credit 0 and the state {0, 0, 0}.
+ * Otherwise, with r = min(rank_dev[s], k), ceil_rho(x) = ceil(x * num / den),
+ * (p, previous) = (peer, credit_dev[s]) when owner == the held id + 1 and
+ * (0, 0) when not, and fresh = the largest rank among this call's QF_OK
+ * reports for the slot:
+ *   1. peer = max(p, fresh)
+ *   2. peer >= k: credit = sent_dev[s] (the peer is satisfied, nothing is left
+ *      to send: qf_gen_select_dev(credit_dev, sent_dev, 1, 0) does not list it)
+ *   3. else c = max(previous, ceil_rho(r))        (every unit of rank is worth
+ *                                                 rho frames)
+ *   4. with a QF_OK report in this call, c = max(c, sent_dev[s] +
+ *      ceil_rho(max(0, r - peer)))                (a request for what the peer
+ *      lacks of what this node holds; the same report twice in one call changes
+ *      nothing, in a later call it asks again: when to report is the host's
+ *      retransmission policy)
+ *   5. credit = min(c, cap)
+ * and the state becomes {held id + 1, peer, 0}.  With num == den and no report
+ * credit = min(rank, k, cap), the budget rank - sent of qf_emit_frames_sel_dev.
+ * win_dev, rank_dev, sent_dev and reports_dev are only read.
+ * Returns QF_EINVAL for k outside 1..256, den == 0, num < den, num > 65535,
+ * cap == 0, cap > 2^20, G == 0, G > 2^24, flags or reserved != 0, a NULL ctx,
+ * shape, win_dev, rank_dev, sent_dev, fb_state_dev or credit_dev, reports_dev
+ * NULL with N_max > 0, win_dev not 8-byte or reports_dev / fb_state_dev not
+ * 16-byte aligned.
+ * Kernels: a memset of G u32 of workspace, k_credit_reports (a lane per report:
+ * one 32-bit atomicMax of rank + 1 per QF_OK report; not launched with N_max 0)
+ * and k_credit_apply (a lane per slot).  A maximum does not depend on the
+ * order, so no output depends on the order of waves.
+ * ------------------------------------------------------------------------- */
+typedef struct qf_rank_report {
+    uint64_t id;
+    uint32_t rank;
+    uint32_t reserved;
+} qf_rank_report; /* 16 bytes */
+
+#define QF_REPORT_APPEND 1u   /* qf_rank_report_sel_dev flags: append at *n_reports_dev instead of starting at 0 */
+
+int qf_rank_report_sel_dev(qf_ctx *ctx, uint32_t k, const qf_gen_sel *sel, const uint64_t *win_dev,
+                           const uint32_t *rank_dev, uint32_t N_max, uint32_t flags,
+                           qf_rank_report *reports_dev, uint32_t *n_reports_dev, uint32_t *n_left_dev);
+
+typedef struct qf_credit_shape {
+    uint32_t k;               /* 1..256 */
+    uint32_t num;             /* rho = num / den >= 1, num <= 65535 */
+    uint32_t den;             /* >= 1 */
+    uint32_t cap;             /* the most a generation may ever have sent, 1..2^20 */
+    uint32_t flags;           /* 0 */
+    uint32_t reserved;        /* 0 */
+} qf_credit_shape;
+
+int qf_credit_update_dev(qf_ctx *ctx, const qf_credit_shape *shape, uint32_t G, const uint64_t *win_dev,
+                         const uint32_t *rank_dev, const uint32_t *sent_dev, uint32_t N_max,
+                         const qf_rank_report *reports_dev, const uint32_t *n_reports_dev,
+                         uint8_t *fb_state_dev, uint32_t *credit_dev, int32_t *report_status_dev);
+
+/* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations
  * whose (k, r, L) and placement differ per generation -- the ASW-RLNC-X mix
  * of window sizes (adaptive.rs:124-153, BASELINE config C5).  Generations
@@ -1668,6 +1777,11 @@ int qf_parse_frames_dev(qf_ctx *ctx, uint32_t k, uint32_t r, uint32_t L, uint32_
  *                               other in a flat queue; sent_dev grows by what was emitted
  * and the queue's arrays are the flat poll of the next hop.  A source emits its
  * packets as systematic rows, then its repairs with QF_EMIT_APPEND.
+ * Over a lossy hop qf_credit_update_dev runs in front of that select and its
+ * credit_dev stands where rank_dev stood in the select and in the emit; the
+ * receiver writes the reports it reads with qf_rank_report_sel_dev over the
+ * completed list and, appended, over the list of qf_gen_select_dev(rank_dev,
+ * NULL, min_rank 1, flags 0), after its resets.
  * The intermediate rows belong to the caller.
  * ------------------------------------------------------------------------- */
 /* No reference counterpart (a layout rule): P = round_up(3 + k, 16) for k in

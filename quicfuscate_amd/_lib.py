@@ -118,6 +118,14 @@ class EmitShape(ctypes.Structure):
     ]
 
 
+class CreditShape(ctypes.Structure):
+    """qf_credit_shape (ranks, a redundancy ratio num / den and reports to the emission budget)."""
+    _fields_ = [("k", _U32), ("num", _U32), ("den", _U32), ("cap", _U32), ("flags", _U32), ("reserved", _U32)]
+
+
+# qf_rank_report as a numpy record: 16 bytes, what qf_rank_report_sel_dev writes and qf_credit_update_dev reads
+RANK_REPORT_DTYPE = [("id", "<u8"), ("rank", "<u4"), ("reserved", "<u4")]
+QF_REPORT_APPEND = 1   # qf_rank_report_sel_dev flags: append at *n_reports_dev instead of starting at 0
 QF_EMIT_APPEND = 1   # qf_emit_shape.flags: append at *n_frames_dev instead of starting at 0
 QF_DELIVERED_WORDS = 5   # u64 per generation slot of the delivered state: tag, then 256 bits
 QF_SRC_UNKNOWN, QF_SRC_STORED, QF_SRC_RECOVERED, QF_SRC_EARLIER = 0, 1, 2, 3   # out_state of qf_deliver_frames_dev
@@ -284,6 +292,8 @@ _SIGS = {
     "qf_deliver_frames_dev": (_I, [_P, ctypes.POINTER(DeliverShape), _U32] + [_P] * 16),
     "qf_deliver_frames_sel_dev": (_I, [_P, ctypes.POINTER(DeliverShape), ctypes.POINTER(GenSel)] + [_P] * 16),
     "qf_emit_frames_sel_dev": (_I, [_P, ctypes.POINTER(EmitShape), ctypes.POINTER(GenSel)] + [_P] * 19),
+    "qf_rank_report_sel_dev": (_I, [_P, _U32, ctypes.POINTER(GenSel), _P, _P, _U32, _U32, _P, _P, _P]),
+    "qf_credit_update_dev": (_I, [_P, ctypes.POINTER(CreditShape), _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

@@ -263,6 +263,35 @@ hipError_t launch_emit_count(const EmitPlanArgs& a, hipStream_t st);
 hipError_t launch_emit_place(const EmitPlanArgs& a, hipStream_t st);   // after launch_emit_count, same stream
 // max_frames: the most frames the plan can have emitted; grid_cap as above
 hipError_t launch_emit_frames(EmitFramesArgs a, uint64_t max_frames, uint32_t grid_cap, hipStream_t st);
+// qf_rank_report_sel_dev and qf_credit_update_dev (qf_credit.hip; DESIGN.md
+// 3.21).  A report is one 16-byte record {id lo, id hi, rank, 0}, a slot's
+// feedback state one {owner lo, owner hi, peer, 0} with owner the id + 1.
+struct ReportSelArgs {
+    const uint32_t* sel;          // [n_max]
+    const uint32_t* n_sel;        // nullptr: n_max
+    const uint64_t* win;          // [G_src]
+    const uint32_t* rank;         // [G_src]
+    const uint32_t* head;         // with append: a copy of *n_reports from before the launch
+    uint4* reports;               // [N_max]
+    uint32_t* n_reports;
+    uint32_t* n_left;             // nullable
+    uint32_t n_max, G_src, k, N_max, append;
+};
+struct CreditArgs {
+    const uint64_t* win;          // [G]
+    const uint32_t* rank;         // [G]
+    const uint32_t* sent;         // [G]
+    const uint4* reports;         // [N_max], nullptr with N_max 0
+    const uint32_t* n_reports;    // nullptr: N_max
+    uint32_t* fresh;              // workspace [G], zeroed: the call's largest reported rank + 1 per slot
+    uint4* state;                 // [G]
+    uint32_t* credit;             // [G]
+    int32_t* report_status;       // [N_max], nullable
+    uint32_t G, N_max, k, num, den, cap;
+};
+hipError_t launch_report_sel(const ReportSelArgs& a, hipStream_t st);
+hipError_t launch_credit_reports(const CreditArgs& a, hipStream_t st);   // after fresh is zeroed; N_max >= 1
+hipError_t launch_credit_apply(const CreditArgs& a, hipStream_t st);     // after launch_credit_reports, same stream
 hipError_t launch_mul_slice(const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n,
                             const uint8_t* explog, int num_cus, hipStream_t st);
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t n, uint64_t seed, uint64_t word_offset,

@@ -1053,6 +1053,55 @@ def emit_frames_sel(sel, n_sel, rows, ids, frames, frame_len, frame_off, frame_i
         _opt(entry_count), _opt(entry_status)), "emit_frames_sel")
 
 
+QF_REPORT_APPEND = L.QF_REPORT_APPEND
+RANK_REPORT_DTYPE = L.RANK_REPORT_DTYPE
+
+
+def rank_report_sel(sel, n_sel, win, rank, reports, n_reports, k: int, *, n_max: int, G_src: int, N_max: int,
+                    n_left=None, append: bool = False, ctx: Optional[Context] = None) -> None:
+    """qf_rank_report_sel_dev: what this node holds of the listed slots as
+    16-byte records (RANK_REPORT_DTYPE) in reports [N_max]: the id of win
+    [G_src] u64 and min(rank [G_src], k), k for a closed entry, and the hole
+    {UINT64_MAX, 0, 0} for an empty entry or a slot >= G_src.  n_reports [1]
+    receives the new length, n_left [1] (optional) the records that did not
+    fit.  append: start at n_reports[0] instead of 0."""
+    _need(win, 8 * G_src, "win")
+    _need(rank, 4 * G_src, "rank")
+    _need(reports, 16 * N_max, "reports (16 bytes per record)")
+    _need(n_reports, 4, "n_reports")
+    _need(n_left, 4, "n_left")
+    gs = _gen_sel(sel, n_sel, n_max, G_src)
+    ctx = ctx or default_context()
+    check(L._lib().qf_rank_report_sel_dev(
+        ctx.handle, k, ctypes.byref(gs), _opt(win), _opt(rank), N_max, QF_REPORT_APPEND if append else 0,
+        _opt(reports), _opt(n_reports), _opt(n_left)), "rank_report_sel")
+
+
+def credit_update(win, rank, sent, fb_state, credit, k: int, *, G: int, num: int = 1, den: int = 1, cap: int,
+                  N_max: int = 0, reports=None, n_reports=None, report_status=None,
+                  ctx: Optional[Context] = None) -> None:
+    """qf_credit_update_dev: credit [G] u32, the budget gen_select and
+    emit_frames_sel take as rank beside sent, from the local rank [G], the ratio
+    num / den, the cap and the peer's reports ([N_max] records, n_reports [1]
+    optional: N_max).  fb_state [G * 16] bytes, zeroed once, remembers per slot
+    the generation and the highest rank reported for it; win [G] u64 is the
+    node's window.  report_status [N_max] i32 (optional) receives QF_OK /
+    QF_ESTALE / QF_ENOTREADY / QF_EINVAL per report."""
+    _need(win, 8 * G, "win")
+    _need(rank, 4 * G, "rank")
+    _need(sent, 4 * G, "sent")
+    _need(fb_state, 16 * G, "fb_state (16 bytes per slot)")
+    _need(credit, 4 * G, "credit")
+    _need(reports, 16 * N_max, "reports (16 bytes per record)")
+    _need(n_reports, 4, "n_reports")
+    _need(report_status, 4 * N_max, "report_status")
+    ctx = ctx or default_context()
+    sh = L.CreditShape(k, num, den, cap, 0, 0)
+    check(L._lib().qf_credit_update_dev(
+        ctx.handle, ctypes.byref(sh), G, _opt(win), _opt(rank), _opt(sent), N_max, _opt(reports), _opt(n_reports),
+        _opt(fb_state), _opt(credit), _opt(report_status)), "credit_update")
+
+
 # ---------------------------------------------------------------------------
 # Packet / MemoryPool / Encoder / Decoder (encoder.rs, decoder.rs, optimize.rs)
 # ---------------------------------------------------------------------------
