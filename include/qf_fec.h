@@ -1303,8 +1303,9 @@ int qf_emit_frames_sel_dev(qf_ctx *ctx, const qf_emit_shape *shape, const qf_gen
  * 16-byte record; the sender turns its own ranks, a redundancy ratio and those
  * records into credit_dev, the array that qf_gen_select_dev and
  * qf_emit_frames_sel_dev take as rank_dev beside sent_dev: "the number of
- * frames a generation may have sent in total".  How the records travel back is
- * the host's business, as the outer header of a frame is.
+ * frames a generation may have sent in total".  The records travel back as
+ * the feedback packets of qf_frame_reports_dev / qf_parse_report_frames_dev
+ * below, or any other way the host likes.
  *   id        a wire generation id (< 2^62); UINT64_MAX is a hole the applier
  *             skips (with status QF_EINVAL)
  *   rank      what the reporting node holds of it, 0..k; k for a generation it
@@ -1405,6 +1406,114 @@ int qf_credit_update_dev(qf_ctx *ctx, const qf_credit_shape *shape, uint32_t G, 
                          const uint32_t *rank_dev, const uint32_t *sent_dev, uint32_t N_max,
                          const qf_rank_report *reports_dev, const uint32_t *n_reports_dev,
                          uint8_t *fb_state_dev, uint32_t *credit_dev, int32_t *report_status_dev);
+
+/* ---------------------------------------------------------------------------
+ * The reports on the wire.  A feedback packet is
+ *   byte 0       0x02  (a data frame starts with 0x00 coded / 0x01 systematic,
+ *                so a demultiplexer can tell the two directions apart)
+ *   bytes 1..2   c, the number of entries, big-endian u16, c >= 1
+ *   c entries of 10 bytes: the wire generation id as a big-endian u64 (< 2^62),
+ *                then the rank as a big-endian u16 (0..k; 256 needs the high byte)
+ * so 3 + 10 c bytes, without padding, checksum or varint: integrity and
+ * encryption belong to the outer transport, as they do for data frames.
+ * qf_report_frame_capacity(max_len), host only: the entries a packet of at most
+ * max_len bytes holds, (max_len - 3) / 10 for max_len 13..65535, else 0.
+ * Packet slot p of pkts_dev is bytes [p * stride, p * stride + stride).
+ *
+ * qf_frame_reports_dev: a report array as packets.  N = min(*n_reports_dev,
+ * N_max) (N_max with n_reports_dev NULL), per = qf_report_frame_capacity(
+ * max_len).  A record is sendable iff id < 2^62, rank <= k and reserved == 0;
+ * every other record, the hole UINT64_MAX included, is skipped.  The S sendable
+ * records among the first N keep their order: number i is entry i % per of
+ * packet i / per.  P = min(ceil(S / per), F_max) packets are written, packet p
+ * from byte 0 of slot p with c_p = min(per, S - p * per) entries and
+ * pkt_len_dev[p] = 3 + 10 c_p; *n_pkts_dev = P; *n_left_dev (nullable) = S -
+ * min(S, F_max * per), the sendable records that did not fit; *n_skipped_dev
+ * (nullable) = N - S.  No byte of a slot outside [0, pkt_len) is written, no
+ * slot and no pkt_len_dev entry at or beyond P; the report array is only read,
+ * and a record at or behind N is not looked at.
+ * Returns QF_EINVAL, before any device work, for a NULL ctx, shape,
+ * reports_dev, pkts_dev, pkt_len_dev or n_pkts_dev, k outside 1..256, max_len
+ * outside 13..65535, F_max == 0, N_max == 0, N_max > 2^24, flags != 0, stride %
+ * 16 != 0, stride < max_len, or reports_dev / pkts_dev not 16-byte aligned.
+ * Kernels: k_fbw_count (a lane per record, the blocks' sums) and k_fbw_pack (the
+ * prefix over the sums; ten byte stores per sendable record, the header and
+ * the length from the lane with a packet's entry 0).
+ *
+ * qf_parse_report_frames_dev: a flat poll of packets as a report array.  F =
+ * min(*n_pkts_dev, F_max) (F_max with n_pkts_dev NULL).  Packet f < F with len =
+ * pkt_len_dev[f] is QF_OK iff 3 <= len <= min(max_len, stride), byte 0 is 0x02,
+ * c >= 1 and len == 3 + 10 c; every other packet is QF_EINVAL and contributes
+ * nothing (len 0 included, as an empty frame is for the frame parsers).  No
+ * byte at or beyond min(len, stride) of a slot is read, and none when len < 3.
+ * base = min(*n_reports_dev, N_max) with QF_REPORT_APPEND in flags, else 0.  The
+ * entries of the QF_OK packets follow each other in packet order, then entry
+ * order; entry i of all T goes to reports_dev[base + i] as {id, rank, 0} when
+ * base + i < N_max.  *n_reports_dev = min(base + T, N_max); *n_left_dev
+ * (nullable) = base + T - *n_reports_dev (saturating at UINT32_MAX).  Nothing is
+ * written below base or at and beyond the new length.  For f < F only, each
+ * nullable: pkt_status_dev[f] the status; pkt_first_dev[f] = base + the entries
+ * of the QF_OK packets in front of f for a QF_OK packet (saturating at
+ * 0xFFFFFFFE), 0xFFFFFFFF otherwise: with it a host attributes records to the
+ * peer a packet came from; pkt_count_dev[f] = c for a QF_OK packet, else 0.
+ * Entry values are not judged: an id >= 2^62 or a rank > k goes through and gets
+ * its QF_EINVAL from qf_credit_update_dev, the one place that decides.
+ * Returns QF_EINVAL, before any device work, for a NULL ctx, shape, pkts_dev,
+ * pkt_len_dev, reports_dev or n_reports_dev, flag bits other than
+ * QF_REPORT_APPEND, and otherwise as qf_frame_reports_dev.
+ * Kernels: k_fbr_count (a lane per packet: the decision, the blocks' sums),
+ * k_fbr_place (the prefix, the per-packet outputs, the lengths) and
+ * k_fbr_records (a wave per 64 entries of a packet, a record per lane; an
+ * appending call copies *n_reports_dev in front of them).
+ *
+ * qf_report_closed_dev: the report of a closed generation, again.  A receiver
+ * reports a generation's closing once; when that report is lost the sender goes
+ * on emitting, and the frames come back from qf_gen_window_dev as QF_ECLOSED.
+ * frame_id_dev / frame_status_dev are that call's arrays of this poll, M =
+ * min(*n_frames_dev, F_max) (F_max with n_frames_dev NULL).  Slot s < G_src is
+ * marked iff some frame f < M has frame_status_dev[f] == QF_ECLOSED,
+ * frame_id_dev[f] < 2^62, frame_id_dev[f] % G_src == s and win_dev[s] holds
+ * exactly that id with the closed flag set: a status the window does not back
+ * up is ignored, and nothing is read through a bad id.  One record {id, k, 0}
+ * per marked slot, in ascending slot order, goes to reports_dev from base (0, or
+ * min(*n_reports_dev, N_max) with QF_REPORT_APPEND) while it is below N_max;
+ * *n_reports_dev and *n_left_dev (nullable) as in qf_rank_report_sel_dev.  Any
+ * number of frames of a generation give one record.  Meant to run appended
+ * behind the two report calls of a poll.
+ * Returns QF_EINVAL for k outside 1..256, G_src == 0 or > 2^24, F_max == 0,
+ * N_max == 0, unknown flag bits, a NULL ctx, frame_id_dev, frame_status_dev,
+ * win_dev, reports_dev or n_reports_dev, win_dev not 8-byte or reports_dev not
+ * 16-byte aligned.
+ * Kernels: a memset of G_src u32 of workspace, k_closed_mark (a lane per frame;
+ * every writer of a slot's flag writes the same value), the two kernels of
+ * qf_gen_select_dev over the flags and k_report_sel over their list.  No output
+ * depends on the order of waves.
+ * ------------------------------------------------------------------------- */
+typedef struct qf_report_wire_shape {
+    uint32_t k;               /* 1..256 */
+    uint32_t max_len;         /* the most bytes a feedback packet may have, 13..65535 */
+    uint32_t F_max;           /* packet slots, >= 1 */
+    uint32_t flags;           /* pack: 0; parse: 0 or QF_REPORT_APPEND */
+    uint64_t stride;          /* bytes per packet slot, % 16 == 0, >= max_len */
+} qf_report_wire_shape;
+
+uint32_t qf_report_frame_capacity(uint32_t max_len);
+
+int qf_frame_reports_dev(qf_ctx *ctx, const qf_report_wire_shape *shape, uint32_t N_max,
+                         const qf_rank_report *reports_dev, const uint32_t *n_reports_dev,
+                         uint8_t *pkts_dev, uint32_t *pkt_len_dev, uint32_t *n_pkts_dev,
+                         uint32_t *n_left_dev, uint32_t *n_skipped_dev);
+
+int qf_parse_report_frames_dev(qf_ctx *ctx, const qf_report_wire_shape *shape,
+                               const uint8_t *pkts_dev, const uint32_t *pkt_len_dev, const uint32_t *n_pkts_dev,
+                               uint32_t N_max, qf_rank_report *reports_dev, uint32_t *n_reports_dev,
+                               uint32_t *n_left_dev, int32_t *pkt_status_dev,
+                               uint32_t *pkt_first_dev, uint32_t *pkt_count_dev);
+
+int qf_report_closed_dev(qf_ctx *ctx, uint32_t k, uint32_t G_src, uint32_t F_max,
+                         const uint64_t *frame_id_dev, const int32_t *frame_status_dev, const uint32_t *n_frames_dev,
+                         const uint64_t *win_dev, uint32_t N_max, uint32_t flags,
+                         qf_rank_report *reports_dev, uint32_t *n_reports_dev, uint32_t *n_left_dev);
 
 /* ---------------------------------------------------------------------------
  * Heterogeneous batches (SURVEY 8(b) qf_gen_desc): one call over generations

@@ -123,6 +123,11 @@ class CreditShape(ctypes.Structure):
     _fields_ = [("k", _U32), ("num", _U32), ("den", _U32), ("cap", _U32), ("flags", _U32), ("reserved", _U32)]
 
 
+class ReportWireShape(ctypes.Structure):
+    """qf_report_wire_shape (rank reports to feedback packets and back)."""
+    _fields_ = [("k", _U32), ("max_len", _U32), ("F_max", _U32), ("flags", _U32), ("stride", _U64)]
+
+
 # qf_rank_report as a numpy record: 16 bytes, what qf_rank_report_sel_dev writes and qf_credit_update_dev reads
 RANK_REPORT_DTYPE = [("id", "<u8"), ("rank", "<u4"), ("reserved", "<u4")]
 QF_REPORT_APPEND = 1   # qf_rank_report_sel_dev flags: append at *n_reports_dev instead of starting at 0
@@ -294,6 +299,11 @@ _SIGS = {
     "qf_emit_frames_sel_dev": (_I, [_P, ctypes.POINTER(EmitShape), ctypes.POINTER(GenSel)] + [_P] * 19),
     "qf_rank_report_sel_dev": (_I, [_P, _U32, ctypes.POINTER(GenSel), _P, _P, _U32, _U32, _P, _P, _P]),
     "qf_credit_update_dev": (_I, [_P, ctypes.POINTER(CreditShape), _U32, _P, _P, _P, _U32, _P, _P, _P, _P, _P]),
+    "qf_report_frame_capacity": (_U32, [_U32]),
+    "qf_frame_reports_dev": (_I, [_P, ctypes.POINTER(ReportWireShape), _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "qf_parse_report_frames_dev": (_I, [_P, ctypes.POINTER(ReportWireShape), _P, _P, _P, _U32, _P, _P, _P, _P, _P,
+                                        _P]),
+    "qf_report_closed_dev": (_I, [_P, _U32, _U32, _U32, _P, _P, _P, _P, _U32, _U32, _P, _P, _P]),
     "qf_fec_config_default": (None, [ctypes.POINTER(FecConfig)]),
     "qf_fec_config_validate": (_I, [ctypes.POINTER(FecConfig)]),
     "qf_mode_params_for": (_I, [ctypes.c_int32, _U32, _P, _P]),

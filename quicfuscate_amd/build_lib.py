@@ -32,7 +32,7 @@ SOURCES = ["qf_kernels.hip", "qf_api.hip", "qf_objects.hip", "qf_bs.hip", "qf_ad
            "qf_gf16.hip", "qf_objects16.hip", "qf_wiedemann.hip", "qf_gf16_bs.hip",
            "qf_gf16_fft.hip", "qf_recode.hip", "qf_rank.hip", "qf_relay.hip", "qf_store.hip", "qf_select.hip",
            "qf_poll.hip", "qf_window.hip", "qf_partial.hip", "qf_deliver.hip", "qf_emit.hip",
-           "qf_credit.hip"]
+           "qf_credit.hip", "qf_fbwire.hip"]
 # (k, r) Cauchy configurations that get a bit-sliced assembly kernel
 # (bs_codegen.py); every other shape runs the general v_perm kernel.
 BS_CONFIGS = [(64, 16), (64, 10), (32, 16), (16, 16), (16, 1), (32, 5), (48, 8), (96, 15)]
@@ -201,6 +201,10 @@ RESOURCE_RULES = {
     # the feedback kernels hold one 16-byte record or state and a few counters
     # per lane: exactly these three kernels, no scratch
     "qf_credit.hip": _Rule(("k_report_sel", "k_credit_reports", "k_credit_apply"), 3, every=True),
+    # the feedback packets' kernels hold one record or one packet's count and a
+    # prefix per lane: exactly these six kernels, no scratch
+    "qf_fbwire.hip": _Rule(("k_fbw_count", "k_fbw_pack", "k_fbr_count", "k_fbr_place", "k_fbr_records",
+                            "k_closed_mark"), 6, every=True),
 }
 # the sources compiled with resource-usage remarks
 REMARK_SOURCES = ("qf_gf16_bs.hip", *RESOURCE_RULES)

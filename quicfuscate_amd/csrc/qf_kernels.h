@@ -292,6 +292,57 @@ struct CreditArgs {
 hipError_t launch_report_sel(const ReportSelArgs& a, hipStream_t st);
 hipError_t launch_credit_reports(const CreditArgs& a, hipStream_t st);   // after fresh is zeroed; N_max >= 1
 hipError_t launch_credit_apply(const CreditArgs& a, hipStream_t st);     // after launch_credit_reports, same stream
+// qf_frame_reports_dev, qf_parse_report_frames_dev and qf_report_closed_dev
+// (qf_fbwire.hip).  A feedback packet is 0x02 | c (BE u16) | c
+// entries of {id BE u64, rank BE u16}; per = (max_len - 3) / 10 entries at most.
+constexpr uint32_t kFbPerBlock = 64;                   // records / packets of a block (one wave, one per lane)
+constexpr uint32_t kFbRecordBlocks = 1u << 20;         // k_fbr_records' grid bound: the rest is strided
+struct FbPackArgs {
+    const uint4* reports;         // [N_max]
+    const uint32_t* n_reports;    // nullptr: N_max
+    uint8_t* pkts;                // [F_max] slots of stride bytes
+    uint32_t* pkt_len;            // [F_max]
+    uint32_t* n_pkts;
+    uint32_t* n_left;             // nullable
+    uint32_t* n_skipped;          // nullable
+    uint32_t* sums;               // workspace [blocks]: the sendable records of each block
+    uint64_t stride;
+    uint32_t N_max, k, per, F_max, blocks;
+};
+hipError_t launch_fbw_count(const FbPackArgs& a, hipStream_t st);
+hipError_t launch_fbw_pack(const FbPackArgs& a, hipStream_t st);        // after launch_fbw_count, same stream
+struct FbParseArgs {
+    const uint8_t* pkts;          // [F_max] slots of stride bytes
+    const uint32_t* pkt_len;      // [F_max]
+    const uint32_t* n_pkts;       // nullptr: F_max
+    const uint32_t* head;         // with append: a copy of *n_reports from before the launches
+    uint4* reports;               // [N_max]
+    uint32_t* n_reports;
+    uint32_t* n_left;             // nullable
+    int32_t* pkt_status;          // [F_max], nullable
+    uint32_t* pkt_first;          // [F_max], nullable
+    uint32_t* pkt_count;          // [F_max], nullable
+    uint32_t* cnt;                // workspace [F_max]: the entries of a QF_OK packet, else 0
+    uint32_t* first;              // workspace [F_max]: min(where the packet's records begin, N_max)
+    uint32_t* sums;               // workspace [blocks]
+    uint64_t stride;
+    uint32_t F_max, N_max, max_len, per, append, blocks;
+    uint32_t chunks;              // ceil(per / 64): the waves of one packet in k_fbr_records
+    uint32_t rec_blocks;          // derived by launch_fbr_records: its grid
+};
+uint32_t fb_parse_blocks(uint32_t F_max);
+hipError_t launch_fbr_count(const FbParseArgs& a, hipStream_t st);
+hipError_t launch_fbr_place(const FbParseArgs& a, hipStream_t st);      // after launch_fbr_count, same stream
+hipError_t launch_fbr_records(FbParseArgs a, hipStream_t st);           // after launch_fbr_place, same stream
+struct ClosedMarkArgs {
+    const uint64_t* frame_id;     // [F_max]
+    const int32_t* frame_status;  // [F_max]
+    const uint32_t* n_frames;     // nullptr: F_max
+    const uint64_t* win;          // [G_src]
+    uint32_t* flags;              // workspace [G_src], zeroed: 1 for a marked slot
+    uint32_t F_max, G_src;
+};
+hipError_t launch_closed_mark(const ClosedMarkArgs& a, hipStream_t st);
 hipError_t launch_mul_slice(const uint8_t* a, const uint8_t* b, uint8_t* out, uint64_t n,
                             const uint8_t* explog, int num_cus, hipStream_t st);
 hipError_t launch_fill_splitmix(uint8_t* dst, uint64_t n, uint64_t seed, uint64_t word_offset,

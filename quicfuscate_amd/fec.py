@@ -1077,6 +1077,82 @@ def rank_report_sel(sel, n_sel, win, rank, reports, n_reports, k: int, *, n_max:
         _opt(reports), _opt(n_reports), _opt(n_left)), "rank_report_sel")
 
 
+def report_frame_capacity(max_len: int) -> int:
+    """qf_report_frame_capacity: the entries of a feedback packet of at most max_len bytes (0: no such packet)."""
+    return int(L._lib().qf_report_frame_capacity(max_len))
+
+
+def frame_reports(reports, n_reports, pkts, pkt_len, n_pkts, k: int, *, N_max: int, max_len: int, F_max: int,
+                  stride: int, n_left=None, n_skipped=None, ctx: Optional[Context] = None) -> None:
+    """qf_frame_reports_dev: the sendable records (id < 2^62, rank <= k,
+    reserved 0) among the first n_reports[0] (optional: N_max) of reports
+    [N_max], in order, as feedback packets "0x02 | c BE u16 | c x {id BE u64,
+    rank BE u16}" of at most max_len bytes in the F_max slots of stride bytes of
+    pkts.  pkt_len [F_max] and n_pkts [1] receive the packets' lengths and their
+    number, n_left [1] (optional) the sendable records that did not fit,
+    n_skipped [1] (optional) the records that are not sendable."""
+    _need(reports, 16 * N_max, "reports (16 bytes per record)")
+    _need(n_reports, 4, "n_reports")
+    _need(pkts, F_max * stride, "pkts")
+    _need(pkt_len, 4 * F_max, "pkt_len")
+    _need(n_pkts, 4, "n_pkts")
+    _need(n_left, 4, "n_left")
+    _need(n_skipped, 4, "n_skipped")
+    ctx = ctx or default_context()
+    sh = L.ReportWireShape(k, max_len, F_max, 0, stride)
+    check(L._lib().qf_frame_reports_dev(
+        ctx.handle, ctypes.byref(sh), N_max, _opt(reports), _opt(n_reports), _opt(pkts), _opt(pkt_len), _opt(n_pkts),
+        _opt(n_left), _opt(n_skipped)), "frame_reports")
+
+
+def parse_report_frames(pkts, pkt_len, n_pkts, reports, n_reports, k: int, *, N_max: int, max_len: int, F_max: int,
+                        stride: int, n_left=None, pkt_status=None, pkt_first=None, pkt_count=None,
+                        append: bool = False, ctx: Optional[Context] = None) -> None:
+    """qf_parse_report_frames_dev: the entries of the well-formed packets among
+    the first n_pkts[0] (optional: F_max) slots of pkts, in packet and entry
+    order, as records in reports [N_max] from 0 (append: from n_reports[0]);
+    n_reports [1] receives the new length, n_left [1] (optional) the records
+    that did not fit.  pkt_status / pkt_first / pkt_count [F_max] (optional)
+    receive QF_OK / QF_EINVAL, the position of a packet's first record
+    (0xFFFFFFFF: none) and its entries.  Entry values are not judged here:
+    credit_update decides."""
+    _need(pkts, F_max * stride, "pkts")
+    _need(pkt_len, 4 * F_max, "pkt_len")
+    _need(n_pkts, 4, "n_pkts")
+    _need(reports, 16 * N_max, "reports (16 bytes per record)")
+    _need(n_reports, 4, "n_reports")
+    _need(n_left, 4, "n_left")
+    _need(pkt_status, 4 * F_max, "pkt_status")
+    _need(pkt_first, 4 * F_max, "pkt_first")
+    _need(pkt_count, 4 * F_max, "pkt_count")
+    ctx = ctx or default_context()
+    sh = L.ReportWireShape(k, max_len, F_max, QF_REPORT_APPEND if append else 0, stride)
+    check(L._lib().qf_parse_report_frames_dev(
+        ctx.handle, ctypes.byref(sh), _opt(pkts), _opt(pkt_len), _opt(n_pkts), N_max, _opt(reports), _opt(n_reports),
+        _opt(n_left), _opt(pkt_status), _opt(pkt_first), _opt(pkt_count)), "parse_report_frames")
+
+
+def report_closed(frame_id, frame_status, n_frames, win, reports, n_reports, k: int, *, G_src: int, F_max: int,
+                  N_max: int, n_left=None, append: bool = False, ctx: Optional[Context] = None) -> None:
+    """qf_report_closed_dev: one record {id, k, 0} per window slot whose closed
+    generation a QF_ECLOSED frame of this poll belongs to (frame_id [F_max] u64
+    and frame_status [F_max] i32 of gen_window, n_frames [1] optional: F_max), in
+    ascending slot order, in reports [N_max] from 0 (append: from n_reports[0]).
+    n_reports [1] receives the new length, n_left [1] (optional) the records
+    that did not fit."""
+    _need(frame_id, 8 * F_max, "frame_id")
+    _need(frame_status, 4 * F_max, "frame_status")
+    _need(n_frames, 4, "n_frames")
+    _need(win, 8 * G_src, "win")
+    _need(reports, 16 * N_max, "reports (16 bytes per record)")
+    _need(n_reports, 4, "n_reports")
+    _need(n_left, 4, "n_left")
+    ctx = ctx or default_context()
+    check(L._lib().qf_report_closed_dev(
+        ctx.handle, k, G_src, F_max, _opt(frame_id), _opt(frame_status), _opt(n_frames), _opt(win), N_max,
+        QF_REPORT_APPEND if append else 0, _opt(reports), _opt(n_reports), _opt(n_left)), "report_closed")
+
+
 def credit_update(win, rank, sent, fb_state, credit, k: int, *, G: int, num: int = 1, den: int = 1, cap: int,
                   N_max: int = 0, reports=None, n_reports=None, report_status=None,
                   ctx: Optional[Context] = None) -> None:
